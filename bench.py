@@ -12,7 +12,9 @@ all-reduce overlapped with backward when N > 1) -> fused AdamW.  The reference's
 
 Prints ONE JSON line on rank 0 (contract in the task statement):
   * value / ms_per_step : wall clock over EXACTLY K steps between barrier + synchronize pairs, max over ranks;
-    median_ms_per_step  : median of the K per-step event intervals (value_median = the rate it gives);
+    median_ms_per_step  : median of the K per-step event intervals (value_median = the rate it gives).
+A plain run does only that: set-up, W warm-up steps, the K timed steps, the line.  With --full it also profiles warm-up steps,
+re-times the dominant kernel inside the timed region and times the CPU baseline, and the line carries:
   * roofline            : the dominant kernel SYMBOL (largest share of a step, found in the profiled warm-up steps), its
     launches bracketed by HIP events on the launch stream INSIDE the timed region, achieved = algorithmic FLOPs (or bytes) of
     that launch / mean event interval; `executed_*` = the FLOPs the kernel really performs (S recomputed in the attention
@@ -22,6 +24,9 @@ Prints ONE JSON line on rank 0 (contract in the task statement):
     bracketed by events): launches/step, mean us, FLOPs and algorithmic bytes per launch, achieved rate and fraction of the
     MFMA / HBM peak, share of the step — so the worst kernel is named;
   * cpu_baseline        : the oracle (CPU restatement of the reference, "port") timed on this box's host cores.
+
+--dump-outputs DIR writes what the last timed step handed its caller as DIR/<name>.npy (see dump_outputs); the inputs, the
+initial weights and the rounding seeds are fixed, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import glob
@@ -98,6 +103,31 @@ def cpu_baseline(cfg, channels, img, classes, sample_bs=8, steps=3):
                       f"({dt:.1f} s per step)"}
 
 
+DUMP_SAMPLE = 1 << 22  # elements kept of each flat parameter / gradient vector: 16 MB of fp32 each
+DUMP_SEED = 20261016
+
+
+def dump_outputs(path, loss, out_name, out, model):
+    """What the last timed step hands its caller, as float32 / float64 .npy files under `path`:
+      loss.npy              the step's loss (float64 scalar);
+      logits.npy            the model output of that step (features.npy for --chammi: the proxy-loss features of its last chunk);
+      params.npy, grads.npy every parameter after the optimiser step and its gradient, flattened and concatenated in
+                            named_parameters() order (a missing gradient counts as zeros); above DUMP_SAMPLE elements, the same
+                            fixed sample of positions for both (sorted, drawn from RandomState(DUMP_SEED))."""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "loss.npy"), np.asarray(loss.item(), dtype=np.float64))
+    np.save(os.path.join(path, out_name + ".npy"), out.float().cpu().numpy())
+    params = [p for _, p in model.named_parameters()]
+    flat_p = torch.cat([p.detach().reshape(-1).float() for p in params])
+    flat_g = torch.cat([(p.grad.detach() if p.grad is not None else torch.zeros_like(p)).reshape(-1).float() for p in params])
+    if flat_p.numel() > DUMP_SAMPLE:
+        idx = np.unique(np.random.RandomState(DUMP_SEED).randint(0, flat_p.numel(), DUMP_SAMPLE))
+        idx = torch.from_numpy(idx).to(flat_p.device)
+        flat_p, flat_g = flat_p[idx], flat_g[idx]
+    np.save(os.path.join(path, "params.npy"), flat_p.cpu().numpy())
+    np.save(os.path.join(path, "grads.npy"), flat_g.cpu().numpy())
+
+
 def newest_pmc_file():
     """profiles/rNN_vM_pmc_traffic.json with the highest (round, version) — numeric, not lexicographic."""
     best, best_key = None, None
@@ -146,10 +176,14 @@ def main():
     ap.add_argument("--channels", type=int, default=8)
     ap.add_argument("--img", type=int, default=224)
     ap.add_argument("--classes", type=int, default=161)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also the profiled warm-up steps (kernel_table), the dominant kernel re-timed in the timed "
+                                                      "region (roofline, step_roofline) and the CPU baseline; a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the loss, the model output and (a fixed sample of) the updated "
+                                                                         "parameters and their gradients after the last timed step as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--atomic-reductions", action="store_true", help="cross-workgroup sums with fp32 atomics (set_deterministic(False)) instead of the default "
                     "deterministic forms (partials through workspaces, fixed-order second pass; bit-reproducible gradients, +0.7 %% step time)")
-    ap.add_argument("--kernel-table", action="store_true", help="also print the per-symbol table to stderr")
+    ap.add_argument("--kernel-table", action="store_true", help="also print the per-symbol table to stderr (implies --full)")
     ap.add_argument("--graph", action="store_true", help="N=1: replay a HIP-graph capture of the step (about 1 %% faster than eager launches); the "
                                                          "dominant kernel's events then come from the profiled warm-up steps, not from the timed region")
     ap.add_argument("--no-graph", action="store_true", help="(default since round 2; kept for old command lines)")
@@ -168,6 +202,9 @@ def main():
     ap.add_argument("--h2d", action="store_true", help="PCIe-inclusive variant (never the headline value): every step's batch comes from pinned "
                                                      "host memory through a copy stream, double-buffered against the previous step")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    full = args.full or args.kernel_table
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -241,6 +278,8 @@ def main():
             chunks.append((name, torch.from_numpy(rs.standard_normal((bsz, len(ids), args.img, args.img)).astype(np.float32)).to(dev),
                            torch.from_numpy(rs.randint(0, args.classes, bsz)).to(dev)))
 
+    last_out = {}  # the model output of the latest step, for --dump-outputs
+
     def chammi_step():
         opt.zero_grad()
         for name, xc, yc in chunks:  # trainer.py:846-935: one backward per chunk, gradients accumulate, one optimiser step
@@ -248,6 +287,7 @@ def main():
             loss = dcv.proxy_loss(model.proxies, feat, yc, model.scale) + extra * 1.0
             loss.backward()
         opt.step()
+        last_out["features"] = feat.detach()  # of the last chunk (detached: holds no autograd graph)
         return loss
 
     def eager_step():
@@ -260,6 +300,7 @@ def main():
         loss = ce(out, y) + extra * 1.0
         loss.backward()
         opt.step()
+        last_out["logits"] = out.detach()
         return loss
 
     graphed = dcv.GraphedTrainStep(model, opt, "train", None, ce, 1.0) if use_graph else None
@@ -271,25 +312,26 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # ---- warm-up: plain steps, then 1-2 fully profiled eager steps (every C-ABI launch bracketed by events) ----
-    n_prof = 2 if args.warmup >= 3 else 1
+    # ---- warm-up: plain steps, then (--full) 1-2 fully profiled eager steps (every C-ABI launch bracketed by events) ----
+    n_prof = (2 if args.warmup >= 3 else 1) if full else 0
     n_back = 1 if args.warmup > n_prof else 0  # the last warm-up step: after the profiled ones, in the timed region's configuration
     for _ in range(max(args.warmup - n_prof - n_back, 0)):
         step()
-    torch.cuda.synchronize()
-    # the profiled steps run on ONE stream, so every launch's duration is its own (with the weight-gradient GEMMs on the second
-    # stream the kernels of the two streams share the chip and their durations overlap: the table would add up to more than the step)
     two_streams = bool(model.wgrad_stream)
-    model.wgrad_stream = False
-    hip.set_profiler(True)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(n_prof):
-        step()
-    e1.record()
-    torch.cuda.synchronize()
-    prof = hip.set_profiler(False)
-    model.wgrad_stream = two_streams
+    if full:
+        torch.cuda.synchronize()
+        # the profiled steps run on ONE stream, so every launch's duration is its own (with the weight-gradient GEMMs on the second
+        # stream the kernels of the two streams share the chip and their durations overlap: the table would add up to more than the step)
+        model.wgrad_stream = False
+        hip.set_profiler(True)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(n_prof):
+            step()
+        e1.record()
+        torch.cuda.synchronize()
+        prof = hip.set_profiler(False)
+        model.wgrad_stream = two_streams
     # A full (generation-2) pass of Python's cyclic collector over everything torch has imported and built by now takes ~110 ms on this
     # host and used to fire inside the timed region (always at the 7th timed step): one 120 ms step at batch 16, absorbed by the launch
     # queue at batch 64.  Collect now and park the survivors in the permanent generation: the collector stays ON, later passes only
@@ -299,19 +341,20 @@ def main():
     gc.freeze()
     if n_back:
         step()  # the timed region's configuration (two streams again), counted in --warmup
-    prof_step_ms = e0.elapsed_time(e1) / n_prof
-    table = table_from(prof, n_prof, prof_step_ms)
-    by_symbol = {}
-    for r in table:
-        by_symbol[r["symbol"]] = by_symbol.get(r["symbol"], 0.0) + r["ms_per_step"]
-    dominant = max(by_symbol, key=by_symbol.get)
-    if args.kernel_table and rank == 0:
+    if full:
+        prof_step_ms = e0.elapsed_time(e1) / n_prof
+        table = table_from(prof, n_prof, prof_step_ms)
+        by_symbol = {}
         for r in table:
-            print(f"  {r['symbol']:28s} {r['shape']:26s} x{r['launches_per_step']:5.1f} {r['avg_us']:8.1f} us  {r['ms_per_step']:7.3f} ms/step "
-                  f"{100 * r['share_of_step']:5.1f} %  " + (f"{r.get('achieved_tflops', 0):7.1f} TF/s ({100 * r.get('frac', 0):4.1f} % alg / "
-                  f"{100 * r.get('frac_executed', 0):4.1f} % exec, {r.get('flop_per_byte')} FLOP/B -> {r.get('bound')})" if r.get("gflop") else f"{r.get('achieved_gbps', 0):7.0f} GB/s"), file=sys.stderr)
+            by_symbol[r["symbol"]] = by_symbol.get(r["symbol"], 0.0) + r["ms_per_step"]
+        dominant = max(by_symbol, key=by_symbol.get)
+        if args.kernel_table and rank == 0:
+            for r in table:
+                print(f"  {r['symbol']:28s} {r['shape']:26s} x{r['launches_per_step']:5.1f} {r['avg_us']:8.1f} us  {r['ms_per_step']:7.3f} ms/step "
+                      f"{100 * r['share_of_step']:5.1f} %  " + (f"{r.get('achieved_tflops', 0):7.1f} TF/s ({100 * r.get('frac', 0):4.1f} % alg / "
+                      f"{100 * r.get('frac_executed', 0):4.1f} % exec, {r.get('flop_per_byte')} FLOP/B -> {r.get('bound')})" if r.get("gflop") else f"{r.get('achieved_gbps', 0):7.0f} GB/s"), file=sys.stderr)
 
-    # ---- timed region: EXACTLY K steps; events only around the dominant symbol's launches (eager) ----
+    # ---- timed region: EXACTLY K steps; (--full) events only around the dominant symbol's launches (eager) ----
     if use_graph:
         graphed(x, y)  # capture (plus its own eager warm-up steps)
         step = lambda: graphed(x, y)  # noqa: E731
@@ -353,7 +396,7 @@ def main():
         nonlocal picks0, syncs0
         syncs0 = model.host_syncs
         picks0 = sum(model.feature_extractor.patch_embed.counter.values()) if args.hcs else 0  # channel draws so far (HCS histogram)
-        if not use_graph:
+        if full and not use_graph:
             hip.set_profiler(True, only=[dominant])
         marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
         sync()
@@ -365,7 +408,7 @@ def main():
             marks[i + 1].record()
         sync()
         dt_ = time.perf_counter() - t0
-        live_ = None if use_graph else hip.set_profiler(False)
+        live_ = hip.set_profiler(False) if full and not use_graph else None
         step_ms_ = [marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps)]
         med_ = float(np.median(step_ms_))
         if os.environ.get("DCV_BENCH_STEP_TIMES") and rank == 0:
@@ -384,14 +427,8 @@ def main():
         order = [True, False]
     else:
         order = [bool(args.overlap) if dp is not None and (args.overlap or args.no_overlap) else (dp.overlap if dp is not None else None)]
-    def build_line(dt, med_ms, live, final_loss, chosen_mode):
-        """The JSON line from one timed region (rank 0 only; None elsewhere)."""
-        if rank != 0:
-            return None
-        B, C, H = args.batch, args.channels, {"tiny": 3, "small": 6, "base": 12, "distill": 6}[args.arch]
-        headline = (args.arch, C, args.img, args.batch, args.classes) == ("small", 8, 224, 64, 161) and not args.hcs and not args.chammi
-        n = (args.img // 16) ** 2
-        N = C * n + 1
+    def full_fields(dt, live, headline):
+        """--full: the roofline of the dominant symbol, the step's roofline and the per-symbol table."""
         # ---- roofline of the dominant symbol ----
         src = live if live is not None else prof
         recs = [(k, r) for k, r in src.items() if k[0] == dominant and r["ev"]]
@@ -479,6 +516,19 @@ def main():
                     r["valu_mfma_coexec_frac"] = v["valu_mfma_coexec_frac"]
                     r["lds_bank_conflict_frac"] = round((v.get("lds_bank_conflict_cycles") or 0.0) / max(v.get("lds_active_cycles") or 1.0, 1.0), 4)
                     r["sq_counter_source"] = "profiles/" + os.path.basename(sq_files[-1])
+        return {"roofline": roof, "step_roofline": step_roof,
+                "kernel_table_mode": "per-launch durations from the profiled warm-up steps, run on one stream (exclusive); "
+                                     "ms_per_step and share_of_step refer to that one-stream step",
+                "kernel_table": table[:24]}
+
+    def build_line(dt, med_ms, live, final_loss, chosen_mode):
+        """The JSON line from one timed region (rank 0 only; None elsewhere)."""
+        if rank != 0:
+            return None
+        B, C, H = args.batch, args.channels, {"tiny": 3, "small": 6, "base": 12, "distill": 6}[args.arch]
+        headline = (args.arch, C, args.img, args.batch, args.classes) == ("small", 8, 224, 64, 161) and not args.hcs and not args.chammi
+        n = (args.img // 16) ** 2
+        N = C * n + 1
         exec_gf = TRAIN_GFLOP_PER_IMG - (DEAD_GFLOP_PER_IMG if model.cls_only_tail else 0.0)
         imgs = args.batch * world * args.steps / dt
         imgs_med = args.batch * world / (med_ms * 1e-3)
@@ -520,12 +570,9 @@ def main():
                           if args.hcs else {}),
                        **({"chammi": "12-channel model, sub-batches Allen 3ch / HPA 4ch / CP 5ch (N = 589 / 785 / 981 tokens), proxy main loss, "
                                      "3 forward/backward passes + 1 optimiser step per step; img/s counts the images of all three"} if args.chammi else {})},
-            "roofline": roof,
-            "step_roofline": step_roof,
-            "kernel_table_mode": "per-launch durations from the profiled warm-up steps, run on one stream (exclusive); "
-                                 "ms_per_step and share_of_step refer to that one-stream step",
-            "kernel_table": table[:24],
         }
+        if full:
+            line.update(full_fields(dt, live, headline))
         if dp is not None:
             steps_run = args.warmup + args.steps
             line["dp"] = {"world_size": dist.get_world_size(), "backend": dist.get_backend(), "buckets_launched": dp.buckets_launched,
@@ -537,7 +584,7 @@ def main():
                           "rccl_channels_requested": os.environ.get("NCCL_MAX_NCHANNELS"),
                           "rccl_channels_in_use": None,  # filled in below, once the communicator is gone and its log complete
                           "reserved_cus": dp.reserved_cus}
-        if world == 1 and not args.no_cpu_baseline:
+        if full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(cfg, args.channels, args.img, args.classes)
         return line
 
@@ -595,6 +642,9 @@ def main():
     line = build_line(dt, med_ms, live, final_loss, chosen_mode)  # None on every rank but 0
     if line is not None:
         line["status"] = "ok"
+    if args.dump_outputs and rank == 0:
+        out_name, out = ("logits", graphed.static_out) if use_graph else next(iter(last_out.items()))
+        dump_outputs(args.dump_outputs, loss, out_name, out, model)
     if use_dp:
         dist.barrier()
         dist.destroy_process_group()

@@ -745,6 +745,39 @@ def test_bench_two_ranks_as_the_driver_launches_it(gpu_device):
     print(f"two ranks on one GPU over gloo: {line['value']:.0f} img/s, modes {line['dp']['modes']}")
 
 
+@pytest.mark.timeout(600)
+def test_bench_plain_and_full_runs_dump_the_same_outputs(gpu_device, tmp_path):
+    """`bench.py --dump-outputs DIR`: a plain run (the headline line only) and a --full run (profiled warm-up steps, events around the dominant
+    kernel in the timed region) of the same arguments write float32 / float64 arrays of at most 64 MB, and the same ones bit for bit (deterministic
+    reductions, fixed inputs and seeds); only the --full line carries the roofline and the kernel table."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    base = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--batch", "4"]
+    runs = {}
+    for mode, extra in (("plain", []), ("full", ["--full", "--no-cpu-baseline"])):
+        out = tmp_path / mode
+        r = subprocess.run(base + extra + ["--dump-outputs", str(out)], cwd=root, capture_output=True, text=True, timeout=500)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        line = json.loads(lines[0])
+        assert line["status"] == "ok" and line["steps"] == 3 and line["ms_per_step"] > 0
+        assert abs(line["value"] - 4 / (line["ms_per_step"] / 1e3)) <= 0.02 * line["value"]
+        assert ("roofline" in line and "kernel_table" in line) == (mode == "full")
+        assert "cpu_baseline" not in line
+        arrays = {f[:-4]: np.load(out / f) for f in sorted(os.listdir(out))}
+        assert set(arrays) == {"loss", "logits", "params", "grads"}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        assert arrays["logits"].shape == (4, 161) and arrays["params"].shape == arrays["grads"].shape
+        assert np.isfinite(arrays["loss"]) and abs(float(arrays["loss"]) - line["config"]["final_loss"]) <= 1e-5
+        runs[mode] = arrays
+    for k in runs["plain"]:
+        assert np.array_equal(runs["plain"][k], runs["full"][k]), k
+
+
 def test_base_width_train_step(gpu_device):
     """DiChaViT-Base dimensions (D = 768, 12 heads, MLP 3072; BASELINE config 5's architecture) on a small image:
     one training step against the oracle — exercises every kernel at the wider layout (LN/ortho lanes, GEMM N tiles

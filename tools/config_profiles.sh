@@ -4,7 +4,7 @@
 ROOT=$GRAFT_REPO_ROOT; OUT=$ROOT/gpurun_out/${1:-r05_cfg}; mkdir -p $OUT
 cd /tmp; export TMPDIR=/tmp
 run() { name=$1; shift
-  (cd $ROOT && timeout -k 10 400 python3 bench.py --no-cpu-baseline "$@" > $OUT/${name}_bench.json 2> $OUT/${name}_bench.err); tail -1 $OUT/${name}_bench.json | cut -c1-160
+  (cd $ROOT && timeout -k 10 400 python3 bench.py --full --no-cpu-baseline "$@" > $OUT/${name}_bench.json 2> $OUT/${name}_bench.err); tail -1 $OUT/${name}_bench.json | cut -c1-160
   rm -rf /tmp/cfgstats_$name
   timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/cfgstats_$name -o s -- python3 $ROOT/bench.py --no-graph --no-cpu-baseline "$@" > $OUT/${name}_stats.log 2>&1
   find /tmp/cfgstats_$name -name "*kernel_stats.csv" -exec cp {} $OUT/${name}_kernel_stats.csv \;

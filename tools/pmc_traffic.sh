@@ -3,7 +3,7 @@
 # passes for HBM traffic (FETCH_SIZE, WRITE_SIZE).  Small summaries under gpurun_out/v5/ (raw traces are deleted on the box).
 set -e
 ROOT=$GRAFT_REPO_ROOT; OUT=$ROOT/gpurun_out/${1:-r02_v1}; mkdir -p $OUT
-cd $ROOT && timeout -k 10 600 python3 bench.py > $OUT/bench.json 2> $OUT/bench.err && tail -1 $OUT/bench.json | cut -c1-200
+cd $ROOT && timeout -k 10 600 python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err && tail -1 $OUT/bench.json | cut -c1-200
 cd /tmp; export TMPDIR=/tmp
 rm -rf /tmp/dcvstats
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/dcvstats -o s -- python3 $ROOT/bench.py --steps 5 --warmup 2 --no-graph --no-cpu-baseline > $OUT/stats.log 2>&1 && echo stats done
