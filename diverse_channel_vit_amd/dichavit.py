@@ -24,6 +24,8 @@ import contextlib
 import math
 import os
 import random
+import types
+import weakref
 from collections import Counter, defaultdict
 from typing import Dict, List, Optional
 
@@ -255,6 +257,36 @@ class ChannelVisionTransformer(_Holder):
         nn.init.trunc_normal_(self.pos_embed, std=0.02, a=-2.0, b=2.0)
         nn.init.trunc_normal_(self.cls_token, std=0.02, a=-2.0, b=2.0)
         self.apply(self._init_weights)
+        # weak link to the DiChaViT that owns this encoder (its arena, operand copies and input affine run get_last_selfattention): set by
+        # DiChaViT.__init__ / __setstate__; no state_dict key, no submodule, dropped from pickles (a weakref cannot be pickled)
+        self._owner = None
+
+    def __getstate__(self):
+        state = dict(super().__getstate__())
+        state.pop("_owner", None)
+        return state
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        self.__dict__.setdefault("_owner", None)
+
+    def get_last_selfattention(self, x, extra_tokens={}, chunk="", layer_idx=-1, *, query_rows=None) -> Optional[torch.Tensor]:
+        """models/dichavit.py:654-663: the softmax attention of block `layer_idx` over the tokens that block sees, fp32 [B, H, N, N] on x's
+        device, detached (an inspection API: no gradient).  The tokens are prepared as forward() prepares them (chunk looked up in the
+        mapper — the reference's default "" raises KeyError as there —, HCS sampling and token drop in train mode, the same input checks);
+        extra_tokens is accepted and ignored, as in the reference.  Only blocks 0 .. layer_idx run; no N x N score matrix of the other blocks
+        is ever formed (dcv_attn_probs_rows writes this block's probabilities once, from the forward's qkv and LSE).
+
+        layer_idx < 0 counts from the end (-1, the default, is the last block).  DEPARTURE from the reference, whose loop tests
+        `i == layer_idx` and so returns None for every negative value — including its own default — evidently meant as DINO's "last
+        self-attention".  layer_idx >= depth or < -depth returns None, as the reference does for out-of-range values.
+        query_rows=r (keyword-only extension): only the query rows [0, r) — row 0 is CLS — [B, H, r, N]; makes CLS maps possible where the
+        full map does not fit (DiChaViT-B, 64 channels at 224 x 224: N = 12 545, 7.55 GB per image)."""
+        owner = self._owner() if self._owner is not None else None
+        if owner is None:
+            raise RuntimeError("get_last_selfattention runs through the DiChaViT that owns this encoder (its parameter arena and operand "
+                               "copies); this ChannelVisionTransformer is not linked to one")
+        return owner._probe_attention(x, chunk, layer_idx, query_rows)
 
     @staticmethod
     def _init_weights(m):  # dichavit.py:509-516
@@ -354,6 +386,7 @@ class DiChaViT(nn.Module):
         else:
             self.scale = np.sqrt(1.0 / config.temperature)
         self.adaptive_interface = nn.ParameterList([self.proxies])  # :812 (state_dict alias key)
+        self.feature_extractor._owner = weakref.ref(self)  # get_last_selfattention (re-linked by __setstate__: deepcopy / unpickle)
         # --- HIP-path state (not part of the state_dict) ---
         self._arena = None
         self._grad_arena = None
@@ -391,6 +424,12 @@ class DiChaViT(nn.Module):
         self._sr_seed = None  # device int32 word, bumped after every stochastically rounded refresh
         # last block on the CLS rows only (exact: the encoder output is norm(x)[:, 0]); DCV_CLS_TAIL=0 computes every row
         self.cls_only_tail = os.environ.get("DCV_CLS_TAIL", "1") != "0"
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        fe = self._modules.get("feature_extractor")
+        if fe is not None:
+            fe._owner = weakref.ref(self)  # a copy's encoder runs on the copy's weights
 
     # ---------------------------------------------------------------------------------------
     # arena management
@@ -457,9 +496,11 @@ class DiChaViT(nn.Module):
         self._qdesc = torch.tensor(qdesc, dtype=torch.int64, device=device)
         self._qbias = torch.empty(len(self.feature_extractor.blocks), 3 * Dm, dtype=torch.float32, device=device)
 
-    def _bf(self, p, transposed=False):
+    def _bf(self, p, transposed=False, buf=None):
+        """buf: a straight copy other than self._bf16 (the scratch copy of get_last_selfattention)."""
         o = self._enc_off[self._w_index[id(p)]]
-        buf = self._bf16_t if transposed else self._bf16
+        if buf is None:
+            buf = self._bf16_t if transposed else self._bf16
         v = buf[o:o + p.numel()]
         if p.dim() >= 2:
             R = p.shape[0]
@@ -723,7 +764,11 @@ class DiChaViT(nn.Module):
             out.append(tuple(pair))
         return out
 
-    def _run_forward(self, x, ch_idx_dev, C, E, pos_tab, want_ortho, save, keep=None, st_scale=None, st_shift=None, tok=None):
+    def _run_forward(self, x, ch_idx_dev, C, E, pos_tab, want_ortho, save, keep=None, st_scale=None, st_shift=None, tok=None, probe=None):
+        """probe=(layer, rows): get_last_selfattention — run blocks < layer as the forward does, stop at block `layer` after its norm1 and qkv
+        GEMM and return its attention probabilities [B, H, rows, N] (fp32) instead of the state.  Needs save=False and want_ortho=False.  The
+        model's operand copies (_bf16, _bf16_t, _qbias) and _sr_seed are left alone — a training forward's backward may still read them — and
+        round-to-nearest straight copies are cast into scratch instead."""
         fe = self.feature_extractor
         D, H = self.dim, fe.num_heads
         P = fe.patch_size
@@ -734,7 +779,16 @@ class DiChaViT(nn.Module):
         dev = x.device
         bf, f32 = torch.bfloat16, torch.float32
         ps = bool(self.attn_prescaled)  # pre-scaled q for this forward AND its backward (kept in the saved state)
-        self._refresh_operand_copies(stochastic=bool(save) and self.training and self.stochastic_weight_rounding, prescale_q=ps)
+        if probe is None:
+            self._refresh_operand_copies(stochastic=bool(save) and self.training and self.stochastic_weight_rounding, prescale_q=ps)
+            wbuf, qbias = None, self._qbias
+        else:
+            assert not save and not want_ortho
+            wbuf, qbias = torch.empty_like(self._bf16), torch.empty_like(self._qbias)
+            hip.cast_bf16(self._arena, wbuf, self._enc_size)
+            if ps:
+                hip.cast_scaled_ranges(self._arena, wbuf, qbias, self._qdesc, self._qdesc.shape[0], 64, (64 ** -0.5) * math.log2(math.e))
+        wb = lambda p: self._bf(p, buf=wbuf)  # noqa: E731
         pe = fe.patch_embed
         # (channels, positions) structure of the embedding rows the tokeniser epilogue adds: (C, n) normally, (1, C*n) when the
         # positional table is per token (the reference's early-out, _pos_table)
@@ -746,7 +800,7 @@ class DiChaViT(nn.Module):
         xs = torch.empty(B, N, D, dtype=f32, device=dev)
         Y = torch.empty(B * T, D, dtype=f32, device=dev) if want_ortho else None
         Ec, pc = E.contiguous(), pos_tab.contiguous()
-        hip.gemm_nt(Xp, self._bf(pe.proj.weight), hip.EPI_PATCH, xs, bias=pe.proj.bias, out2=Y, aux=Ec, aux2=pc, T=T, n=ntok,
+        hip.gemm_nt(Xp, wb(pe.proj.weight), hip.EPI_PATCH, xs, bias=pe.proj.bias, out2=Y, aux=Ec, aux2=pc, T=T, n=ntok,
                     ldo=D, ldo2=D, ldaux=D)
         hip.fill_cls(xs, fe.cls_token, pc, B, N * D, D)
         stats = torch.zeros(B, 2, dtype=f32, device=dev)
@@ -793,9 +847,16 @@ class DiChaViT(nn.Module):
                 mean1, rstd1 = torch.empty(M, dtype=f32, device=dev), torch.empty(M, dtype=f32, device=dev)
                 hip.ln_fwd(xcur, blk.norm1.weight, blk.norm1.bias, u1, mean1, rstd1, M, D, LN_EPS)
             qkv = torch.empty(M, 3 * D, dtype=bf, device=dev)
-            hip.gemm_nt(u1, self._bf(blk.attn.qkv.weight), hip.EPI_BIAS_BF16, qkv, bias=self._qbias[bi] if ps else blk.attn.qkv.bias)
+            hip.gemm_nt(u1, wb(blk.attn.qkv.weight), hip.EPI_BIAS_BF16, qkv, bias=qbias[bi] if ps else blk.attn.qkv.bias)
             o = torch.empty(M, D, dtype=bf, device=dev)
             lse = torch.empty(B, H, N, dtype=f32, device=dev)
+            if probe is not None and bi == probe[0]:
+                # the probed block: LSE of its query rows from the forward kernel, then the probabilities written once; no later block runs
+                rows = probe[1]
+                hip.attn_fwd(qkv, o, lse, B, N, H, D // H, scale, nq=rows, prescaled=ps)
+                probs = torch.empty(B, H, rows, N, dtype=f32, device=dev)
+                hip.attn_probs(qkv, lse, probs, B, N, H, D // H, scale, nq=rows, prescaled=ps)
+                return probs
             if tail:
                 # The encoder's output is read at the CLS row only (norm(x)[:, 0], dichavit.py:651-652), so in the LAST block
                 # every token-wise op after the attention needs the CLS rows alone, and the attention only the CLS query
@@ -805,7 +866,7 @@ class DiChaViT(nn.Module):
                 o_c = o.view(B, N, D)[:, 0].contiguous()
                 x_c = xcur.view(B, N, D)[:, 0].contiguous()
                 xmid = torch.empty(B, D, dtype=f32, device=dev)
-                hip.gemm_nt(o_c, self._bf(blk.attn.proj.weight), hip.EPI_BIAS_RESID_F32, xmid, bias=blk.attn.proj.bias, aux=x_c,
+                hip.gemm_nt(o_c, wb(blk.attn.proj.weight), hip.EPI_BIAS_RESID_F32, xmid, bias=blk.attn.proj.bias, aux=x_c,
                             **(dict(aux2=dsc[0], T=1) if dsc else {}))
                 R = B  # rows the rest of this block works on
             else:
@@ -817,10 +878,10 @@ class DiChaViT(nn.Module):
                     # attn.proj + residual AND norm2 from the accumulators of one launch (dcv_gemm_nt_resid_ln): no re-read of xmid
                     u2 = torch.empty(R, D, dtype=bf, device=dev)
                     mean2, rstd2 = torch.empty(R, dtype=f32, device=dev), torch.empty(R, dtype=f32, device=dev)
-                    hip.gemm_nt_resid_ln(o, self._bf(blk.attn.proj.weight), blk.attn.proj.bias, xcur, xmid, blk.norm2.weight, blk.norm2.bias,
+                    hip.gemm_nt_resid_ln(o, wb(blk.attn.proj.weight), blk.attn.proj.bias, xcur, xmid, blk.norm2.weight, blk.norm2.bias,
                                          LN_EPS, u2, mean2, rstd2, **(dict(branch_scale=dsc[0], T=N) if dsc else {}))
                 else:
-                    hip.gemm_nt(o, self._bf(blk.attn.proj.weight), hip.EPI_BIAS_RESID_F32, xmid, bias=blk.attn.proj.bias, aux=xcur,
+                    hip.gemm_nt(o, wb(blk.attn.proj.weight), hip.EPI_BIAS_RESID_F32, xmid, bias=blk.attn.proj.bias, aux=xcur,
                                 **(dict(aux2=dsc[0], T=N) if dsc else {}))
             if tail or not fuse_ln:
                 u2 = torch.empty(R, D, dtype=bf, device=dev)
@@ -828,18 +889,18 @@ class DiChaViT(nn.Module):
                 hip.ln_fwd(xmid, blk.norm2.weight, blk.norm2.bias, u2, mean2, rstd2, R, D, LN_EPS)
             z = torch.empty(R, 4 * D, dtype=bf, device=dev)  # GELU'(pre-activation), saved for the backward
             hact = torch.empty(R, 4 * D, dtype=bf, device=dev)
-            hip.gemm_nt(u2, self._bf(blk.mlp.fc1.weight), hip.EPI_BIAS_GELU_BF16, z, bias=blk.mlp.fc1.bias, out2=hact)
+            hip.gemm_nt(u2, wb(blk.mlp.fc1.weight), hip.EPI_BIAS_GELU_BF16, z, bias=blk.mlp.fc1.bias, out2=hact)
             xout = torch.empty(R, D, dtype=f32, device=dev) if (save or tail) else xmid
             nxt = fe.blocks[bi + 1] if bi + 1 < len(fe.blocks) else None
             if fuse_ln and not tail and nxt is not None:
                 # mlp.fc2 + residual AND the NEXT block's norm1 (its full rows are needed even when that block is the CLS-only tail: keys and values)
                 un = torch.empty(M, D, dtype=bf, device=dev)
                 mn, rn = torch.empty(M, dtype=f32, device=dev), torch.empty(M, dtype=f32, device=dev)
-                hip.gemm_nt_resid_ln(hact, self._bf(blk.mlp.fc2.weight), blk.mlp.fc2.bias, xmid, xout, nxt.norm1.weight, nxt.norm1.bias, LN_EPS,
+                hip.gemm_nt_resid_ln(hact, wb(blk.mlp.fc2.weight), blk.mlp.fc2.bias, xmid, xout, nxt.norm1.weight, nxt.norm1.bias, LN_EPS,
                                      un, mn, rn, **(dict(branch_scale=dsc[1], T=R // B) if dsc else {}))
                 pre_ln = (un, mn, rn)
             else:
-                hip.gemm_nt(hact, self._bf(blk.mlp.fc2.weight), hip.EPI_BIAS_RESID_F32, xout, bias=blk.mlp.fc2.bias, aux=xmid,
+                hip.gemm_nt(hact, wb(blk.mlp.fc2.weight), hip.EPI_BIAS_RESID_F32, xout, bias=blk.mlp.fc2.bias, aux=xmid,
                             **(dict(aux2=dsc[1], T=R // B) if dsc else {}))
             if save:
                 L.update(drop=dsc)
@@ -1154,15 +1215,49 @@ class DiChaViT(nn.Module):
 
     def _forward_impl(self, x: torch.Tensor, chunk_name: str, training_chunks: Optional[str] = None, init_first_layer=None,
                       new_channel_init=None, **kwargs):
+        self._check_input(x)
+        if self._dp is not None and self.training:
+            self._dp.begin_forward()
+        tk = self._prepare_tokens(x, chunk_name, training_chunks, new_channel_init)
+        self._cur_scale, self._cur_shift = tk.scale, tk.shift  # the affine rows of the channels used by this forward
+        x, C, n, want_ortho, cur_channels, channel_embed = tk.x, tk.C, tk.n, tk.want_ortho, tk.cur_channels, tk.channel_embed
+        lam_o, lam_p = tk.lam_o, tk.lam_p
+        pe = self.feature_extractor.patch_embed
+        feat, stats = _EncoderFn.apply(self, tk.ch_idx_dev, C, want_ortho, tk.keep, tk.tok, x, tk.E_tok, tk.pos_tab, *self._enc_params)
+        # --- regularisers (tiny tensors; models/loss_fn.py) ---
+        extra = 0
+        if want_ortho:
+            extra = extra + lam_o * self._ortho_from_stats(stats, C, n)
+        if lam_p > 0 and (self.training or True):
+            # the reference evaluates the proxy term in eval mode too and discards it; skip it there
+            if self.training:
+                prox = pe.channel_emb_proxies.index_select(0, self._index_tensor(cur_channels, torch.int64, x.device))  # global ids (:401)
+                if (self.fused_proxy_loss and prox.dtype == torch.float32 and channel_embed.dtype == torch.float32
+                        and hip.proxy_loss_supported(C, self.dim)):
+                    extra = extra + lam_p * _ChannelProxyLossFn.apply(prox, channel_embed, float(pe.channel_scale))
+                else:
+                    extra = extra + lam_p * _proxy_loss(prox, channel_embed, torch.eye(C, device=x.device), float(pe.channel_scale))
+        out = self.classifer_head(feat)  # :855
+        if self.training:
+            if isinstance(extra, int) and extra == 0:
+                extra = out.new_zeros(())  # :857-858 (a device-side fill: torch.tensor(0.0, device=...) is a synchronising host-to-device copy)
+            return out, extra
+        return out
+
+    @staticmethod
+    def _check_input(x: torch.Tensor) -> None:
         if not x.is_cuda:
             raise RuntimeError("diverse_channel_vit_amd runs only on an MI355X: move the model and the batch to the GPU "
                                "(there is no CPU fallback; the CPU restatement lives in oracle/ and is test infrastructure)")
         hip.load()
+
+    def _prepare_tokens(self, x: torch.Tensor, chunk_name: str, training_chunks: Optional[str], new_channel_init):
+        """The host side of ChannelVisionTransformer.prepare_tokens (dichavit.py:554-626) shared by forward() and get_last_selfattention: input
+        checks, channel embedding rows (HCS draw in train mode, leave-one-out rows at eval), positional table, tokeniser channel index, the
+        token-drop keep list and the input affine rows of the channels used.  Everything that draws random numbers for a forward draws here."""
         fe = self.feature_extractor
         pe = fe.patch_embed
         cfg = self.cfg
-        if self._dp is not None and self.training:
-            self._dp.begin_forward()
         self._ensure_arena(x.device)
         x = x.contiguous() if x.dtype == torch.uint8 else x.contiguous().float()
         if x.dtype == torch.uint8 and self._in_scale is None:
@@ -1197,13 +1292,13 @@ class DiChaViT(nn.Module):
         pos_tab = self._pos_table(C, n, Hi, Wi)
         ch_idx_dev = self._index_tensor(idx, torch.int32, x.device)
         keep = self._token_keep(C, n)
-        self._cur_scale = self._cur_shift = None
+        cur_scale = cur_shift = None
         if self._in_scale is not None:  # gather the affine like channel_embed: by the global ids of the channels used
             if self._in_scale.device != x.device:  # moved to the device once (no pageable copy per step; capture-safe)
                 self._in_scale, self._in_shift = self._in_scale.to(x.device), self._in_shift.to(x.device)
             gi = self._index_tensor(cur_channels, torch.int64, x.device)
-            self._cur_scale = self._in_scale[gi].contiguous()
-            self._cur_shift = self._in_shift[gi].contiguous()
+            cur_scale = self._in_scale[gi].contiguous()
+            cur_shift = self._in_shift[gi].contiguous()
         tok, E_tok = None, channel_embed
         if C > 1 and pos_tab.shape[0] == 1 + C * n:
             # the reference's early-out hit with several channels: token t gets pos_embed[1+t] whatever its channel.  The
@@ -1212,26 +1307,26 @@ class DiChaViT(nn.Module):
             pos_tab = pos_tab + torch.cat([torch.zeros_like(channel_embed[:1]), channel_embed.repeat_interleave(n, dim=0)], dim=0)
             E_tok = torch.zeros_like(channel_embed[:1])
             tok = (1, C * n)
-        feat, stats = _EncoderFn.apply(self, ch_idx_dev, C, want_ortho, keep, tok, x, E_tok, pos_tab, *self._enc_params)
-        # --- regularisers (tiny tensors; models/loss_fn.py) ---
-        extra = 0
-        if want_ortho:
-            extra = extra + lam_o * self._ortho_from_stats(stats, C, n)
-        if lam_p > 0 and (self.training or True):
-            # the reference evaluates the proxy term in eval mode too and discards it; skip it there
-            if self.training:
-                prox = pe.channel_emb_proxies.index_select(0, self._index_tensor(cur_channels, torch.int64, x.device))  # global ids (:401)
-                if (self.fused_proxy_loss and prox.dtype == torch.float32 and channel_embed.dtype == torch.float32
-                        and hip.proxy_loss_supported(C, self.dim)):
-                    extra = extra + lam_p * _ChannelProxyLossFn.apply(prox, channel_embed, float(pe.channel_scale))
-                else:
-                    extra = extra + lam_p * _proxy_loss(prox, channel_embed, torch.eye(C, device=x.device), float(pe.channel_scale))
-        out = self.classifer_head(feat)  # :855
-        if self.training:
-            if isinstance(extra, int) and extra == 0:
-                extra = out.new_zeros(())  # :857-858 (a device-side fill: torch.tensor(0.0, device=...) is a synchronising host-to-device copy)
-            return out, extra
-        return out
+        return types.SimpleNamespace(x=x, C=C, n=n, cur_channels=cur_channels, channel_embed=channel_embed, want_ortho=want_ortho, lam_o=lam_o,
+                                     lam_p=lam_p, pos_tab=pos_tab, ch_idx_dev=ch_idx_dev, keep=keep, tok=tok, E_tok=E_tok, scale=cur_scale,
+                                     shift=cur_shift)
+
+    def _probe_attention(self, x, chunk_name, layer_idx, query_rows):
+        """ChannelVisionTransformer.get_last_selfattention: the tokens as forward() prepares them, then blocks 0 .. layer through _run_forward's
+        probe.  DataParallel's begin_forward() is not called: no gradient leaves this path."""
+        with torch.autocast(device_type="cuda", enabled=False), torch.no_grad():
+            self._check_input(x)
+            tk = self._prepare_tokens(x, chunk_name, None, None)
+            depth = len(self.feature_extractor.blocks)
+            layer_idx = int(layer_idx)
+            if not -depth <= layer_idx < depth:
+                return None
+            N = len(tk.keep) if tk.keep is not None else tk.C * tk.n + 1
+            rows = N if query_rows is None else int(query_rows)
+            if not 1 <= rows <= N:
+                raise ValueError(f"query_rows={query_rows}: expected 1 <= query_rows <= {N} (the tokens this block sees)")
+            return self._run_forward(tk.x, tk.ch_idx_dev, tk.C, tk.E_tok, tk.pos_tab, False, save=False, keep=tk.keep, st_scale=tk.scale,
+                                     st_shift=tk.shift, tok=tk.tok, probe=(layer_idx % depth, rows))
 
     def _ortho_from_stats(self, stats, C, n):
         """loss_fn.py:44-59 on the per-image (pos_sum, neg_sum)."""

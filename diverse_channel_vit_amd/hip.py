@@ -54,6 +54,8 @@ _SIGS = {
     "dcv_attn_bwd_rows_ps": ([_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp], _i),
     "dcv_attn_bwd_dq_rows_ps": ([_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp], _i),
     "dcv_attn_bwd_dkdv_rows_ps": ([_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp], _i),
+    "dcv_attn_probs_rows": ([_vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp], _i),
+    "dcv_attn_probs_rows_ps": ([_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp], _i),
     "dcv_im2col_bf16": ([_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp], _i),
     "dcv_patch_bwd": ([_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp], _i),
     "dcv_gather_tokens": ([_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp], _i),
@@ -388,6 +390,22 @@ def attn_bwd(qkv, o, dO, lse, delta_ws, dqkv, B, N, H, hd, scale, nq=None, presc
     with _timer(lambda: (("attn_bwd_dkdv3p_kernel" if prescaled else "attn_bwd_dkdv2_kernel<false>"), f"B{B} N{N} H{H} Nq{nq}", 3 * prod, 4 * prod, 2.0 * B * (N * 3 * D_ + nq * 1 * D_ + N * 2 * D_))):
         rc = dkdv_fn(_p(qkv), _p(dO), _p(lse), _p(delta_ws), _p(dqkv), B, N, nq, H, hd, scale, _stream())
     _check(rc, "dcv_attn_bwd_dkdv")
+
+
+def attn_probs(qkv, lse, P, B, N, H, hd, scale, nq=None, prescaled=False):
+    """P [B, H, nq, N] fp32 = softmax(q k^T * scale) of the query rows [0, nq) (default: all N) from qkv and the forward's lse
+    (include/dcv.h: dcv_attn_probs_rows).  prescaled: the q part of qkv holds q * scale * log2(e) (dcv_attn_probs_rows_ps; scale unused)."""
+    _req(qkv, torch.bfloat16, "qkv"); _req(lse, torch.float32, "lse"); _req(P, torch.float32, "P")
+    nq_ = N if nq is None else nq
+    if P.numel() < B * H * nq_ * N or lse.numel() < B * H * N:
+        raise ValueError("attn_probs: P holds B*H*nq*N floats, lse B*H*N")
+    with _timer(lambda: (f"attn_probs_kernel<{'true' if prescaled else 'false'}>", f"B{B} N{N} H{H} Nq{nq_}", 2.0 * B * H * nq_ * N * hd, None,
+                         4.0 * B * H * nq_ * N)):
+        if prescaled:
+            rc = load().dcv_attn_probs_rows_ps(_p(qkv), _p(lse), _p(P), B, N, nq_, H, hd, _stream())
+        else:
+            rc = load().dcv_attn_probs_rows(_p(qkv), _p(lse), _p(P), B, N, nq_, H, hd, float(scale), _stream())
+    _check(rc, "dcv_attn_probs_rows")
 
 
 def im2col(x, ch_idx, out, B, Ct, C, H, W, P, scale=None, shift=None):

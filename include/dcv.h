@@ -178,6 +178,14 @@ int dcv_attn_bwd_dq_rows_ps(const void* qkv, const void* o, const void* dO, cons
 int dcv_attn_bwd_dkdv_rows_ps(const void* qkv, const void* dO, const float* lse, const float* ws, void* dqkv, int B, int N, int Nq,
                               int H, int head_dim, float scale, void* stream);
 
+/* Attention probabilities of one block, written once (ChannelVisionTransformer.get_last_selfattention; models/dichavit.py:654-663 returns
+ * softmax(q k^T * scale), models/vit.py:128-129): P [B,H,Nq,N] f32 row-major, row pitch exactly N floats, P[b,h,q,k] = exp(q.k scale - lse[b,h,q])
+ * for the query rows q < Nq (1 <= Nq <= N) and every key k < N.  qkv [B,N,3,H,64] bf16 and lse [B,H,N] (natural log; rows < Nq read) as
+ * dcv_attn_fwd_rows(_ps) produced them; the _ps form takes the pre-scaled q of dcv_attn_fwd_rows_ps.  No atomics: bitwise reproducible, and row
+ * q does not depend on Nq.  Store-bound: writes 4 B H Nq N bytes. */
+int dcv_attn_probs_rows(const void* qkv, const float* lse, float* P, int B, int N, int Nq, int H, int head_dim, float scale, void* stream);
+int dcv_attn_probs_rows_ps(const void* qkv, const float* lse, float* P, int B, int N, int Nq, int H, int head_dim, void* stream);
+
 /* x [B,Ct,H,W] f32 (x_is_u8 == 0: normalised images, the reference's batch format) or u8 (raw pixels), ch_idx int32[C]
  * (device) -> bf16 [B*C*(H/P)*(W/P), P*P] patch rows (dichavit.py:134/210,377).  scale/shift f32[C] (nullable, indexed by
  * gathered position): x*scale[c] + shift[c], i.e. the (x/255 - mean_c)/std_c of the CPU pipeline
