@@ -9,8 +9,10 @@
 //            of the same layers.  Reduction dim is the long one (M = B*N tokens): split over
 //            workgroups, fp32 atomics into the gradient arena.
 //
-// gemm_nt: persistent 256x128 (8 waves, 3-stage LDS-DMA ring) and 256x384 (two 80 KB stages) kernels, geometry below.
+// gemm_nt: persistent 256x128 (8 waves, 3-stage LDS-DMA ring) and 256x384 (two 80 KB stages) kernels, geometry below; for K = 384 the
+//          weight-stationary kernel (a 384-column W slice in registers, 32-row A panels through the ring).
 // gemm_tn: 128x128 register-staged kernel (4 waves) and the 384x128 LDS-DMA ring kernel (8 waves).
+#include <algorithm>
 #include <atomic>
 #include <type_traits>
 #include "dcv_common.hpp"
@@ -1025,6 +1027,184 @@ __global__ __launch_bounds__(512) void gemm_nt384_kernel(GemmNtArgs a) {
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// gemm_nt_ws (round 6): WEIGHT-STATIONARY form of the K = 384 products (N % 384 == 0, bf16-output epilogues).  The 256 x 384 and
+// 256 x 128 kernels are bound by the vector L1's request stream (profiles/r05_x8_*), and most of their read lines re-fetch the W
+// panel once per 256-row tile (392 times per launch).  With K = 384 a 384-column slice of W is 288 KB: it fits the register file.
+// So each workgroup (one per CU, 12 waves = 3 per SIMD) owns one slice, loads it ONCE into MFMA fragment registers (wave w: columns
+// 32 w .. +31 x K 384 = 2 column blocks x 12 k-steps x 4 VGPRs = 96 registers; a 16-byte global load of a W row is exactly one
+// 16x16x32 fragment), and walks 32-row panels of A that arrive through an LDS-DMA ring.  The s = N / 384 workgroups that read the same
+// A panel have neighbouring logical ids on one XCD (xcd_remap), so one of them misses in L2 and the others hit.  A read lines per
+// launch: A s times + W once per CU, against A s times + W 392 times (plus A 3x / 12x for the 256 x 128 tiles).
+// Same MFMA (16x16x32, swapped operands) and the same k order (0 -> 383 into one accumulator from zero) as the other NT kernels,
+// so the outputs are bit-identical to theirs.  Epilogue: after one v_permlane16_swap per register pair a lane holds 8 consecutive
+// columns of one row; a wave's store covers 16 rows x 64 bytes (its 32 columns), neighbouring waves the other half of each line.
+// The GELU-backward's saved GELU'(z) comes through the ring too (LDS-DMA, laid out in the epilogue's lane order), so the k-loop issues
+// no load hipcc counts: every vmcnt wait in the walk is the kernel's own.
+#ifndef DCV_NT_WS
+#define DCV_NT_WS 1
+#endif
+#if DCV_NT_WS
+constexpr int WS_BM = 32, WS_BN = 384, WS_K = 384, WS_WAVES = 12;
+constexpr int WS_A_BYTES = WS_BM * WS_K * 2;     // 24 KB: 6 k-chunks of [32 rows][64] (128-byte rows, swz64n), 24 DMA pieces = 2 per wave
+constexpr int WS_AUX_BYTES = WS_BM * WS_BN * 2;  // 24 KB: [wave][row block][lane] x 16 B, 2 pieces per wave
+template <int EPI>
+struct WsCfg {
+    static constexpr bool AUX = (EPI == DCV_EPI_GELU_BWD_BF16);
+    static constexpr int STAGE = WS_A_BYTES + (AUX ? WS_AUX_BYTES : 0);
+    static constexpr int NS = AUX ? 3 : 6;                                               // ring depth: 144 KB either way
+    static constexpr int ND = AUX ? 4 : 2;                                               // DMA pieces per wave and panel
+    static constexpr int S = 2 * (EPI == DCV_EPI_BIAS_GELU_BF16 ? 2 : 1);               // stores per wave of a full panel
+    static constexpr int SMEM = NS * STAGE;
+};
+
+// s_waitcnt vmcnt(n) for a wave-uniform n that is not a compile-time constant (n <= 24 here)
+__device__ __forceinline__ void ws_wait_vm(int n) {
+    switch (n) {
+#define WS_W(k) \
+    case k: asm volatile("s_waitcnt vmcnt(" #k ")" ::: "memory"); break;
+        WS_W(0) WS_W(1) WS_W(2) WS_W(3) WS_W(4) WS_W(5) WS_W(6) WS_W(7) WS_W(8) WS_W(9) WS_W(10) WS_W(11) WS_W(12)
+        WS_W(13) WS_W(14) WS_W(15) WS_W(16) WS_W(17) WS_W(18) WS_W(19) WS_W(20) WS_W(21) WS_W(22) WS_W(23) WS_W(24)
+#undef WS_W
+        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
+    }
+}
+
+template <int EPI>
+__global__ __launch_bounds__(64 * WS_WAVES) void gemm_nt_ws_kernel(GemmNtArgs a) {
+    using C = WsCfg<EPI>;
+    __shared__ __attribute__((aligned(16))) char smem[C::SMEM];
+    constexpr bool HAS_BIAS = (EPI == DCV_EPI_BIAS_BF16) || (EPI == DCV_EPI_BIAS_GELU_BF16);
+    static_assert(EPI == DCV_EPI_BIAS_BF16 || EPI == DCV_EPI_BIAS_GELU_BF16 || EPI == DCV_EPI_PLAIN_BF16 || EPI == DCV_EPI_GELU_BWD_BF16,
+                  "bf16-output epilogues only");
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r16 = lane & 15, kg = lane >> 4;
+    const int slices = a.N / WS_BN;
+    const int G = gridDim.x;                      // = groups x slices (the host launches whole groups)
+    const int groups = G / slices;
+    const int q = xcd_remap(blockIdx.x, G);       // speed only: the members of a group sit on one XCD
+    const int slice = q % slices, grp = q / slices;
+    const int panels = (a.M + WS_BM - 1) / WS_BM;
+    const int npl = grp < panels ? (panels - grp + groups - 1) / groups : 0;  // panels grp, grp + groups, ...
+    if (npl == 0) return;
+    const int n0 = slice * WS_BN, nw = n0 + 32 * wave;   // the wave's 32 output columns
+    const int ncol = nw + 16 * (kg & 1) + 8 * (kg >> 1);  // the lane's 8 columns in the epilogue
+
+    const unsigned smem_base = __builtin_amdgcn_readfirstlane(lds_addr(smem));
+    // A DMA: piece p = 2 wave + u of a panel: k-chunk p >> 2, rows 8 (p & 3) .. +7; lane -> row lane >> 3, physical chunk lane & 7
+    // holding logical chunk (lane & 7) ^ swz64n(row) (the swizzle on the source, destination linear)
+    int arow[2];
+    unsigned acol[2], adst[2];
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        const int p = 2 * wave + u, kc = p >> 2, row = 8 * (p & 3) + (lane >> 3);
+        arow[u] = row;
+        acol[u] = (unsigned)(64 * kc + (((lane & 7) ^ swz64n(row)) * 8)) * 2;
+        adst[u] = kc * 4096 + (p & 3) * 1024;
+    }
+    auto issue = [&](int t) {  // the DMA pieces of this wave for local panel t into ring slot t % NS
+        const int m0 = __builtin_amdgcn_readfirstlane((grp + t * groups) * WS_BM);
+        const unsigned slot = smem_base + (t % C::NS) * C::STAGE;
+        const bf16_t* ab = a.A + (size_t)m0 * a.lda;
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int rc = min(m0 + arow[u], a.M - 1) - m0;  // the last panel's rows clamp to M - 1 (never stored)
+            glds16s(ab, (unsigned)rc * a.lda * 2 + acol[u], slot + adst[u]);
+        }
+        if constexpr (C::AUX) {  // the wave's own GELU'(z) block: row block i -> 1 KB in lane order
+            const bf16_t* xb = (const bf16_t*)a.aux + (size_t)m0 * a.ldaux;
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                const int rc = min(m0 + 16 * i + r16, a.M - 1) - m0;
+                glds16s(xb, (unsigned)(rc * a.ldaux + ncol) * 2, slot + WS_A_BYTES + (2 * wave + i) * 1024);
+            }
+        }
+    };
+
+    // the weight slice, once: wf[j][s] = W[nw + 16 j + r16][32 s + 8 kg .. +7]
+    bf16x8 wf[2][12];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const bf16_t* wr = a.W + (size_t)(nw + 16 * j + r16) * a.ldw + 8 * kg;
+#pragma unroll
+        for (int s = 0; s < 12; ++s) wf[j][s] = as_bf16x8(*reinterpret_cast<const uint4*>(wr + 32 * s));
+    }
+    float bz[8];
+    if constexpr (HAS_BIAS) load8_f32(a.bias + ncol, bz);
+    // prologue: the first NS - 1 panels in flight (hipcc's wait for the weight registers, at their first use, also drains these: once)
+#pragma unroll
+    for (int t = 0; t < C::NS - 1; ++t)
+        if (t < npl) issue(t);
+    // consume the weight and bias registers HERE: otherwise hipcc's wait for those loads lands at their first use inside the walk and,
+    // blind to the DMAs, drains the ring on every panel
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int s = 0; s < 12; ++s) asm volatile("" : "+v"(wf[j][s]));
+    if constexpr (HAS_BIAS) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) asm volatile("" : "+v"(bz[e]));
+    }
+
+    // per-lane fragment offsets in a stage: k-step s = 2 kc + ks reads logical chunk 4 ks + kg of rows 16 i + r16 (swz64n(16 i + r16) = swz64n(r16))
+    int fo0 = r16 * 128 + ((kg ^ swz64n(r16)) << 4);
+    asm volatile("" : "+v"(fo0));
+    const int fo1 = fo0 ^ 64;
+    bool prev_full = false;  // the previous panel issued exactly S stores per wave
+    for (int t = 0; t < npl; ++t) {
+        // panel t's pieces landed once only younger operations of this wave are outstanding: the pieces of panels t+1 .. t+NS-2 (those
+        // that exist) and the previous panel's stores (counted only when they are known to be exactly S; else the stricter wait)
+        const int ahead = min(C::NS - 2, npl - 1 - t);
+        ws_wait_vm(C::ND * ahead + (prev_full ? C::S : 0));
+        __builtin_amdgcn_s_barrier();  // every wave's pieces of panel t are in LDS; every wave is done with slot (t - 1) % NS
+        if (t + C::NS - 1 < npl) issue(t + C::NS - 1);  // into the slot of panel t - 1
+        const int m0 = (grp + t * groups) * WS_BM;
+        const char* st = smem + (t % C::NS) * C::STAGE;
+        const char* const p0 = st + fo0;
+        const char* const p1 = st + fo1;
+
+        f32x4 acc[2][2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) acc[i][j][r] = 0.f;
+        // the A fragments of k-step s + 1 are read while the MFMAs of step s run (order pinned: left alone, hipcc waits for each
+        // step's reads right before its MFMAs)
+        auto rdA = [&](int s, int i) { return as_bf16x8(lds_read128((s & 1) ? p1 : p0, (s >> 1) * 4096 + i * 2048)); };
+        bf16x8 af[2][2];
+        af[0][0] = rdA(0, 0);
+        af[0][1] = rdA(0, 1);
+#pragma unroll
+        for (int s = 0; s < 12; ++s) {
+            if (s + 1 < 12) {
+                af[(s + 1) & 1][0] = rdA(s + 1, 0);
+                af[(s + 1) & 1][1] = rdA(s + 1, 1);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) acc[i][j] = mfma16(wf[j][s], af[s & 1][i], acc[i][j]);  // operands swapped, as in the other NT kernels
+            __builtin_amdgcn_sched_barrier(0);
+        }
+
+        const bool full = m0 + WS_BM <= a.M;
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            float v[8], x[8];
+            swap_pair8(acc[i][0], acc[i][1], v);  // lane (r16, kg): row 16 i + r16, columns ncol .. +7
+            if constexpr (C::AUX) unpack8_bf16(lds_read128(st + WS_A_BYTES, (2 * wave + i) * 1024 + lane * 16), x);
+            const int m = m0 + 16 * i + r16;
+            if (full || m < a.M) epi_store8<EPI>(a, m, ncol, v, x, bz);
+        }
+        prev_full = full;
+    }
+}
+#endif  // DCV_NT_WS
+
 #ifndef DCV_NT_ALT
 #define DCV_NT_ALT 0
 #endif
@@ -1766,10 +1946,24 @@ static int dcv_cu_count() {
             hipLaunchKernelGGL(KERNEL<DCV_EPI_GELU_BWD_BF16>, dim3(G), dim3(THREADS), 0, s, a);            \
             break;
 
-// which kernel dcv_gemm_nt_ex launches for this problem (DCV_TILE_NARROW / DCV_TILE_WIDE), or a negative error for an illegal forced tile
+// DCV_TILE_AUTO_WS: the weight-stationary kernel from this many rows on (below, its one-off weight load and the few panels per CU
+// do not pay; the 64-row CLS tail stays on the tiled kernels)
+#ifndef DCV_WS_M_MIN
+#define DCV_WS_M_MIN 8192
+#endif
+// which kernel dcv_gemm_nt_ex launches for this problem (DCV_TILE_NARROW / _WIDE / _PAIR / _ALT / _WS), or a negative error for an illegal forced tile
 extern "C" int dcv_gemm_nt_pick(int M, int N, int K, int epilogue, int tile) {
-    if (tile < DCV_TILE_AUTO || tile > DCV_TILE_ALT) return DCV_ERR_SHAPE;
+    if (tile < DCV_TILE_AUTO || tile > DCV_TILE_AUTO_WS) return DCV_ERR_SHAPE;
     const bool legal384 = (N % N3_BN) == 0 && epilogue != DCV_EPI_PATCH;
+    const bool legal_ws = DCV_NT_WS && K == 384 && (N % 384) == 0 &&
+                          (epilogue == DCV_EPI_BIAS_BF16 || epilogue == DCV_EPI_BIAS_GELU_BF16 || epilogue == DCV_EPI_PLAIN_BF16 ||
+                           epilogue == DCV_EPI_GELU_BWD_BF16);
+    if (tile == DCV_TILE_WS) return legal_ws ? DCV_TILE_WS : DCV_ERR_UNSUPPORTED;
+    if (tile == DCV_TILE_AUTO_WS) {
+        // the weight-stationary kernel where it measured faster (tools/gemm_bench.py), else AUTO's choice
+        if (legal_ws && M >= DCV_WS_M_MIN) return DCV_TILE_WS;
+        tile = DCV_TILE_AUTO;
+    }
     if (tile == DCV_TILE_WIDE) return legal384 ? DCV_TILE_WIDE : DCV_ERR_UNSUPPORTED;
     if (tile == DCV_TILE_ALT) return (DCV_NT_ALT && legal384 && epilogue != DCV_EPI_BIAS_RESID_F32) ? DCV_TILE_ALT : DCV_ERR_UNSUPPORTED;
     if (tile == DCV_TILE_NARROW) return DCV_TILE_NARROW;
@@ -1804,7 +1998,7 @@ extern "C" int dcv_gemm_nt_ex(const void* A, int lda, const void* W, int ldw, in
     if (!A || !W || !out) return DCV_ERR_NULL;
     if (M <= 0 || N <= 0 || K <= 0 || (K % 64) != 0 || (N % 8) != 0) return DCV_ERR_SHAPE;
     if ((lda % 8) || (ldw % 8) || (ldo % 8) || ((uintptr_t)A & 15) || ((uintptr_t)W & 15) || ((uintptr_t)out & 15)) return DCV_ERR_ALIGN;
-    if (grid_cap < 0 || tile < DCV_TILE_AUTO || tile > DCV_TILE_ALT) return DCV_ERR_SHAPE;
+    if (grid_cap < 0 || tile < DCV_TILE_AUTO || tile > DCV_TILE_AUTO_WS) return DCV_ERR_SHAPE;
     if (epilogue == DCV_EPI_BIAS_RESID_F32 && aux2 && (T <= 0 || (M % T) != 0)) return DCV_ERR_SHAPE;  // per-sample branch scale: T rows per sample
     // persistent kernels: one workgroup per CU walks the tiles; grid_cap (> 0) lowers the number of workgroups — the data-parallel
     // backward leaves CUs to RCCL's kernels this way (dichavit.py), tests force multi-round walks on small problems
@@ -1815,8 +2009,43 @@ extern "C" int dcv_gemm_nt_ex(const void* A, int lda, const void* W, int ldw, in
     // N = 1536 K = 384 + GELU: 238 -> 218; N = 384 K = 1536: 192 -> 184 (+residual), 154 -> 138 (plain); but N = 384 K = 384:
     // 96 -> 101 (393 tiles on 256 CUs: two rounds for 1.5 rounds of work), and the GELU-backward epilogue (N = 1536, HBM-heavy:
     // 616 MB in + out) 212 -> 220.  tile = DCV_TILE_WIDE forces the 256 x 384 kernel wherever it is legal, DCV_TILE_NARROW never uses it.
-    const int pick = dcv_gemm_nt_pick(M, N, K, epilogue, tile);
+    int pick = dcv_gemm_nt_pick(M, N, K, epilogue, tile);
     if (pick < 0) return pick;
+#if DCV_NT_WS
+    if (pick == DCV_TILE_WS && cap < N / WS_BN) {  // fewer workgroups than weight slices: only the tiled kernels can run under this cap
+        if (tile == DCV_TILE_WS) return DCV_ERR_UNSUPPORTED;
+        pick = dcv_gemm_nt_pick(M, N, K, epilogue, DCV_TILE_AUTO);
+    }
+    if (pick == DCV_TILE_WS) {
+        // whole groups of N / 384 workgroups (one per weight slice), at most one group per 32-row panel; a CU count that the slice count does
+        // not divide leaves the remainder idle (qkv: 85 groups of 3 on 256 CUs)
+        if ((ldo2 % 8) || (ldaux % 8) || ((uintptr_t)out2 & 15) || ((uintptr_t)aux & 15) || ((uintptr_t)bias & 15)) return DCV_ERR_ALIGN;
+        const int slices = N / WS_BN, panels = (M + WS_BM - 1) / WS_BM;
+        const int groups = std::min(cap / slices, panels);
+        const int gw = groups * slices;
+        switch (epilogue) {
+            case DCV_EPI_BIAS_BF16:
+                if (!bias) return DCV_ERR_NULL;
+                hipLaunchKernelGGL(gemm_nt_ws_kernel<DCV_EPI_BIAS_BF16>, dim3(gw), dim3(64 * WS_WAVES), 0, s, a);
+                break;
+            case DCV_EPI_BIAS_GELU_BF16:
+                if (!bias || !out2) return DCV_ERR_NULL;
+                hipLaunchKernelGGL(gemm_nt_ws_kernel<DCV_EPI_BIAS_GELU_BF16>, dim3(gw), dim3(64 * WS_WAVES), 0, s, a);
+                break;
+            case DCV_EPI_PLAIN_BF16:
+                hipLaunchKernelGGL(gemm_nt_ws_kernel<DCV_EPI_PLAIN_BF16>, dim3(gw), dim3(64 * WS_WAVES), 0, s, a);
+                break;
+            case DCV_EPI_GELU_BWD_BF16:
+                if (!aux) return DCV_ERR_NULL;
+                hipLaunchKernelGGL(gemm_nt_ws_kernel<DCV_EPI_GELU_BWD_BF16>, dim3(gw), dim3(64 * WS_WAVES), 0, s, a);
+                break;
+            default:
+                return DCV_ERR_UNSUPPORTED;
+        }
+        DCV_LAUNCH_CHECK();
+        return DCV_OK;
+    }
+#endif
     if (pick == DCV_TILE_WIDE) {
         int g3 = ((M + N3_BM - 1) / N3_BM) * (N / N3_BN);
         if (g3 > cap) g3 = cap;
@@ -1903,7 +2132,7 @@ extern "C" int dcv_gemm_nt_resid_ln(const void* A, int lda, const void* W, int l
 extern "C" int dcv_gemm_nt(const void* A, int lda, const void* W, int ldw, int M, int N, int K, int epilogue,
                            const float* bias, void* out, int ldo, void* out2, int ldo2, const void* aux, int ldaux,
                            const float* aux2, int T, int n, void* stream) {
-    return dcv_gemm_nt_ex(A, lda, W, ldw, M, N, K, epilogue, bias, out, ldo, out2, ldo2, aux, ldaux, aux2, T, n, 0, DCV_TILE_AUTO, stream);
+    return dcv_gemm_nt_ex(A, lda, W, ldw, M, N, K, epilogue, bias, out, ldo, out2, ldo2, aux, ldaux, aux2, T, n, 0, DCV_TILE_AUTO_WS, stream);
 }
 
 // splits / rows per split of a weight-gradient launch (pure function of the problem, the tile and the device's CU count)
