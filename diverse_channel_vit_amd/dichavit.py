@@ -305,12 +305,23 @@ class ChannelVisionTransformer(_Holder):
 class _EncoderFn(torch.autograd.Function):
     """inputs : x [B,Ct,H,W] f32, E [C,D] f32 (channel-embedding rows of this step), pos_tab [1+n,D] f32,
                 then the encoder parameters in arena order (model._enc_params).
-       outputs: CLS feature after the final LayerNorm [B,D] f32, ortho statistics [B,2] f32."""
+       outputs: CLS feature after the final LayerNorm [B,D] f32, ortho statistics [B,2] f32.
+       x gets a gradient when it requires one (dcv_patch_dgrad after the tokeniser's backward).  When only x does — no parameter, no E row,
+       no positional table, no DataParallel reducer — the backward is DATA-ONLY: no weight-gradient GEMM, no gradient arena, no saved Xp."""
 
     @staticmethod
     def forward(ctx, model, ch_idx_dev, C, want_ortho, keep, tok, x, E, pos_tab, *params):
-        st = model._run_forward(x, ch_idx_dev, C, E, pos_tab, want_ortho, save=any(ctx.needs_input_grad), keep=keep,
+        need = ctx.needs_input_grad
+        st = model._run_forward(x, ch_idx_dev, C, E, pos_tab, want_ortho, save=any(need), keep=keep,
                                 st_scale=model._cur_scale, st_shift=model._cur_shift, tok=tok)
+        if need[6]:  # dcv_patch_dgrad's operands: the bf16 projection copy this forward multiplied by, the channel index, the input affine's scale
+            fe = model.feature_extractor
+            P = fe.patch_size
+            st.update(dx_req=True, Wp=model._bf(fe.patch_embed.proj.weight), ch_idx=ch_idx_dev, in_scale=model._cur_scale, Ct=x.shape[1],
+                      Hi=x.shape[2], Wi=x.shape[3], P=P)
+            if not any(need[7:]) and model._dp is None:  # data-only backward: no weight gradient, so the im2col rows are not kept
+                st.pop("Xp", None)
+                st["data_only"] = True
         ctx.model = model
         ctx.st = st
         return st["feat"], st["stats"]
@@ -318,13 +329,17 @@ class _EncoderFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dfeat, dstats):
         model, st = ctx.model, ctx.st
+        if torch.is_grad_enabled():
+            raise RuntimeError("the HIP encoder node has a hand-written first-order backward: create_graph=True (second-order gradients) "
+                               "is not supported")
         ctx.st = None
         if st.get("consumed"):
             raise RuntimeError("the HIP encoder node frees its activations in backward; backward twice is not supported")
         dE, dpos, grads = model._run_backward(st, dfeat.contiguous(), dstats)
+        dx = st.get("dx_out")
         st["consumed"] = True
         st.clear()
-        return (None, None, None, None, None, None, None, dE, dpos) + tuple(grads)
+        return (None, None, None, None, None, None, dx, dE, dpos) + tuple(grads)
 
 
 class _LinearStatsLossFn(torch.autograd.Function):
@@ -924,9 +939,19 @@ class DiChaViT(nn.Module):
         return ga[o:o + p.numel()].view(p.shape)
 
     def _run_backward(self, st, dfeat, dstats):
+        """Returns (dE, dpos, parameter gradients); the input-image gradient, when the state asks for it, goes to st["dx_out"].  Data-only
+        state (st["data_only"]: nothing but x needs a gradient): the gradient arena is not touched, LayerNorm's dgamma / dbeta and d(cls) go to
+        throwaway scratch and no weight-gradient GEMM is launched."""
+        dp = self._dp
+        if st.get("data_only"):
+            fe = self.feature_extractor
+            junk = torch.empty(2, self.dim, dtype=torch.float32, device=dfeat.device)
+            biases = {id(fe.norm.bias)} | {id(b.norm1.bias) for b in fe.blocks} | {id(b.norm2.bias) for b in fe.blocks}
+            # only LayerNorm's and d(cls) slots are written; the weight-gradient slots are requested but never launched
+            g = lambda p: junk[1 if id(p) in biases else 0].view(p.shape) if p.numel() == self.dim else None  # noqa: E731
+            return self._run_backward_body(st, dfeat, dstats, None, g, None, {})
         ga = self._new_grad_arena()
         g = lambda p: self._gview(ga, p)  # noqa: E731
-        dp = self._dp
         # Data parallel: RCCL's all-reduce kernels run beside this backward, one workgroup per channel with 21 KB of LDS each
         # (read from librccl's gfx950 code object).  Neither NT GEMM kernel can share a CU with one (144 KB / 160 KB of the 160),
         # and both deal their tiles statically to one workgroup per CU, so a workgroup whose CU is taken starts late and the
@@ -957,6 +982,7 @@ class DiChaViT(nn.Module):
         dev = dfeat.device
         bf, f32 = torch.bfloat16, torch.float32
         # --- final LayerNorm (CLS rows) ---
+        wgrads = ga is not None  # False: data-only backward (no weight-gradient GEMM)
         fs = st["final_stride"]
         compact = fs == D  # the last block ran on the CLS rows only: its gradients are [B, D] until its attention
         dx = torch.zeros(B if compact else M, D, dtype=f32, device=dev)
@@ -993,6 +1019,8 @@ class DiChaViT(nn.Module):
         readers, held = {}, []
 
         def wgrad(Y, X, gw, gb, key):
+            if not wgrads:
+                return
             if side is None:
                 hip.gemm_tn_acc(Y, X, gw, gb)
                 return
@@ -1010,6 +1038,8 @@ class DiChaViT(nn.Module):
         grp = []
 
         def wgrad_or_collect(Y, X, gw, gb, key, grouped):
+            if not wgrads:
+                return
             if grouped:
                 grp.append((Y, X, gw, gb))
             else:
@@ -1053,7 +1083,7 @@ class DiChaViT(nn.Module):
             R = B if tail else M
             dz_, du_ = (dz[:R], du[:R]) if tail else (dz, du)
             priv = private and not tail
-            plan = self._group_ok(M, D) if (priv and self.wgrad_group) else ()
+            plan = self._group_ok(M, D) if (priv and self.wgrad_group and wgrads) else ()
             grouped = bool(plan)
             # MLP
             if priv:
@@ -1080,7 +1110,8 @@ class DiChaViT(nn.Module):
             if tail:
                 dO_c = du[B:2 * B]  # scratch rows of the same buffer
                 hip.gemm_nt(dxb, self._bf(blk.attn.proj.weight, True), hip.EPI_PLAIN_BF16, dO_c, **nt_kw)
-                hip.gemm_tn_acc(dxb, L["o_c"], g(blk.attn.proj.weight), g(blk.attn.proj.bias))
+                if wgrads:
+                    hip.gemm_tn_acc(dxb, L["o_c"], g(blk.attn.proj.weight), g(blk.attn.proj.bias))
                 dO.view(B, N, D)[:, 0].copy_(dO_c)  # only the CLS rows of dO are read (nq = 1)
                 hip.attn_bwd(L["qkv"], L["o"], dO, L["lse"], delta, dqkv, B, N, H, D // H, scale, nq=1, prescaled=ps)
                 dx_c = dx
@@ -1156,13 +1187,20 @@ class DiChaViT(nn.Module):
         dE = torch.zeros(Ctok, D, dtype=f32, device=dev)
         dpos = torch.zeros(ntok + 1, D, dtype=f32, device=dev)
         hip.patch_bwd(dx, dYl, dYb, dE, dpos, g(fe.cls_token), B, Ctok, ntok, D)
-        hip.gemm_tn_acc(dYb, st["Xp"], g(pe.proj.weight), g(pe.proj.bias))
+        if st.get("dx_req"):
+            # input images: dYb (the token gradients with the ortho term) through the projection's adjoint; the real (C, n), also when the
+            # positional table is per token (tok = (1, C*n)): dYb's rows are (b, c, i, j) either way
+            dxin = torch.empty(B, st["Ct"], st["Hi"], st["Wi"], dtype=f32, device=dev)
+            hip.patch_dgrad(dYb, st["Wp"], st["ch_idx"], dxin, B, st["Ct"], C, st["Hi"], st["Wi"], st["P"], scale=st["in_scale"])
+            st["dx_out"] = dxin
+        if wgrads:
+            hip.gemm_tn_acc(dYb, st["Xp"], g(pe.proj.weight), g(pe.proj.bias))
         if dp is not None:
             dp.grad_ready(ga, *self._range_of([fe.cls_token, pe.proj.bias]))
             dp.flush()
         grads = []
         for p in self._enc_params:
-            grads.append(self._gview(ga, p) if p.requires_grad else None)
+            grads.append(self._gview(ga, p) if (wgrads and p.requires_grad) else None)
         return dE, dpos, grads
 
     def _group_ok(self, M, D):

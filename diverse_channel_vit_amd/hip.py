@@ -58,6 +58,7 @@ _SIGS = {
     "dcv_attn_probs_rows_ps": ([_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp], _i),
     "dcv_im2col_bf16": ([_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp], _i),
     "dcv_patch_bwd": ([_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp], _i),
+    "dcv_patch_dgrad": ([_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp], _i),
     "dcv_gather_tokens": ([_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp], _i),
     "dcv_fill_cls": ([_vp, _vp, _vp, _i, _l, _i, _vp], _i),
     "dcv_ortho_fwd": ([_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp], _i),
@@ -414,6 +415,23 @@ def im2col(x, ch_idx, out, B, Ct, C, H, W, P, scale=None, shift=None):
     _req(x, x.dtype, "x"); _req(ch_idx, torch.int32, "ch_idx")
     _check(load().dcv_im2col_bf16(_p(x), 1 if x.dtype == torch.uint8 else 0, _p(ch_idx), _p(scale), _p(shift), _p(out), B, Ct, C, H, W,
                                   P, _stream()), "dcv_im2col_bf16")
+
+
+def patch_dgrad(dY, W, ch_idx, dx, B, Ct, C, H, Wimg, P, scale=None):
+    """dx [B, Ct, H, W] f32 = the input-image gradient of the tokeniser (include/dcv.h: dcv_patch_dgrad): dY [B*C*n, D] bf16 token gradients,
+    W [D, P*P] bf16 the projection operand the forward used, ch_idx int32 [C], scale f32 [C] (the input affine's, or None).  Every element of dx
+    is written; unsupported shapes (P not 8 / 16, D not 192 / 384 / 768) raise."""
+    _req(dY, torch.bfloat16, "dY"); _req(W, torch.bfloat16, "W"); _req(ch_idx, torch.int32, "ch_idx"); _req(dx, torch.float32, "dx")
+    if scale is not None:
+        _req(scale, torch.float32, "scale")
+    D = W.shape[0]
+    n = (H // P) * (Wimg // P)
+    if W.numel() != D * P * P or dY.shape != (B * C * n, D) or dx.numel() != B * Ct * H * Wimg or ch_idx.numel() != C:
+        raise ValueError("patch_dgrad: dY [B*C*n, D], W [D, P*P], ch_idx [C], dx [B, Ct, H, W]")
+    with _timer(lambda: (f"patch_dgrad_kernel<{P}, {D}>", f"M{B * C * n} D{D} P{P}", 2.0 * B * C * n * D * P * P, None,
+                         2.0 * B * C * n * D + 4.0 * B * Ct * H * Wimg)):
+        rc = load().dcv_patch_dgrad(_p(dY), _p(W), _p(ch_idx), _p(scale), _p(dx), B, Ct, C, H, Wimg, P, D, _stream())
+    _check(rc, "dcv_patch_dgrad")
 
 
 def patch_bwd(dx0, dYloss, dY_bf16, dE, dpos, dcls, B, C, n, D):

@@ -201,6 +201,15 @@ int dcv_im2col_bf16(const void* x, int x_is_u8, const int* ch_idx, const float* 
 /* one pass over d(tokens) f32 [B,1+C*n,D]: dY_bf16 [B*C*n,D] = dx0[:,1:] (+ dYloss) ; dE [C,D], dpos [1+n,D], dcls [D] += */
 int dcv_patch_bwd(const float* dx0, const float* dYloss, void* dY_bf16, float* dE, float* dpos, float* dcls, int B, int C, int n,
                   int D, void* stream);
+/* Input-image gradient of the tokeniser: the adjoint of dcv_im2col_bf16 composed with the patch projection (autograd of the Conv3d and the
+ * channel gather, models/dichavit.py:134/210,377):  dx[b, ch_idx[c], i*P+u, j*P+v] = scale[c] * sum_d dY[(b*C + c)*n + i*(W/P) + j, d] * W[d, u*P+v].
+ * dY bf16 [B*C*n, D] (n = (H/P)(W/P); dcv_patch_bwd's dY_bf16), W bf16 [D, P*P] (the straight operand copy of proj.weight the forward used),
+ * ch_idx int32 [C] distinct positions of [0, Ct), scale f32 [C] nullable and indexed like im2col's (shift has no gradient), dx f32 [B, Ct, H, W].
+ * Writes every element of dx exactly once: channels not in ch_idx and the pixels outside the (H/P)P x (W/P)P window get 0.  No atomics:
+ * bitwise reproducible.  Shapes as dcv_im2col_bf16 (and C <= Ct); P in {8, 16} and D in {192, 384, 768}, else DCV_ERR_UNSUPPORTED; dY and dx
+ * 16-byte aligned. */
+int dcv_patch_dgrad(const void* dY, const void* W, const int* ch_idx, const float* scale, float* dx, int B, int Ct, int C, int H, int W_img,
+                    int P, int D, void* stream);
 /* dropout_tokens_hcs (dichavit.py:568-627): scatter == 0: out[b,k,:] = x[b,idx[k],:] (x [B,N,D] -> out [B,Nk,D]);
  * scatter != 0: out[b,idx[k],:] = x[b,k,:] (x [B,Nk,D] -> out [B,N,D], caller zero-fills out first).  f32, D % 4 == 0. */
 int dcv_gather_tokens(const float* x, const int* idx, float* out, int B, int N, int Nk, int D, int scatter, void* stream);
