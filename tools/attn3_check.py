@@ -57,7 +57,10 @@ def run(h, name, d, nq):
 h0 = hs[0]
 href = C.CDLL(os.path.join(ROOT, "diverse_channel_vit_amd", "libdcv_hip_dkdv2.so"))  # -DDCV_DKDV_FORM=2 build: the second form behind the same entry
 ok = True
-for (B, N, H, nq) in [(1, 64, 1, 64), (2, 256, 2, 256), (1, 77, 3, 77), (2, 320, 6, 320), (3, 1569, 6, 1569), (2, 1569, 6, 1), (2, 600, 6, 33), (1, 4100, 2, 4100)]:
+for (B, N, H, nq) in [(1, 64, 1, 64), (2, 256, 2, 256), (1, 77, 3, 77), (2, 320, 6, 320), (3, 1569, 6, 1569), (2, 1569, 6, 1), (2, 600, 6, 33), (1, 4100, 2, 4100),
+                      # more items than CUs: the workgroups walk several items and the comparison crosses the seams between them, !in_loop (nt < 16: the first two
+                      # and the last) and in_loop (N 981: nt 16, stores and K / V rows overlap on region R); tests/test_attn_seams_gpu.py has the full table
+                      (48, 289, 6, 289), (32, 589, 6, 589), (40, 981, 6, 981), (64, 1569, 6, 1)]:
     d = make(B, N, H, seed=N)
     dq_ref, ws_ref = prep(href, d, nq)
     for h, l in zip(hs, libs):  # dQ (query rows < nq; the rest zero) and the workspace rows, third form against second
