@@ -107,12 +107,21 @@ def evaluate(model, batches: Iterable, chunk_name: str, training_chunks: Optiona
 @torch.inference_mode()
 def dump_features(model, loaders: Dict[str, Iterable], feature_dir: str, feature_file: str = "features.npy",
                   training_chunks: Optional[str] = None, new_channel_init: Optional[str] = None, init_first_layer=None,
-                  channel_combinations: Optional[Sequence[int]] = None, device=None) -> List[str]:
+                  channel_combinations: Optional[Sequence[int]] = None, device=None, layers: Optional[int] = None,
+                  pool: Optional[str] = None) -> List[str]:
     """eval_morphem70k's feature pass (trainer.py:645-690): for every chunk in ``loaders`` (e.g. Allen / HPA / CP) run the
     model in eval mode over the chunk's batches — image tensors, as the CHAMMI test loaders yield (dicts with "image" are
     accepted too) — with ``training_chunks`` and the leave-one-out ``new_channel_init``, concatenate the [b, D] feature
     rows and write them with ``np.save`` to ``<feature_dir>/<chunk>/<feature_file>`` (utils.write_numpy, utils.py:232-235).
-    Returns the written paths; the caller hands ``feature_dir`` to ``morphem.benchmark.run_benchmark`` as the reference does."""
+    Returns the written paths; the caller hands ``feature_dir`` to ``morphem.benchmark.run_benchmark`` as the reference does.
+
+    ``layers=n`` writes what a DINO linear probe uses instead of the model's output: the final-normed CLS rows of the last ``n`` blocks
+    concatenated along the feature axis, [b, n * D] (``get_intermediate_layers``); with ``pool="channel"`` the mean over all patch tokens of
+    the last block is appended, [b, (n + 1) * D].  ``init_first_layer`` is not used on that path.  ``pool`` without ``layers`` raises."""
+    if pool not in (None, "channel"):
+        raise ValueError(f"pool={pool!r}: expected None or 'channel'")
+    if layers is None and pool is not None:
+        raise ValueError("pool needs layers=n (the default writes the model's output)")
     was_training = model.training
     model.eval()
     paths = []
@@ -124,7 +133,15 @@ def dump_features(model, loaders: Dict[str, Iterable], feature_dir: str, feature
                 x = x.to(device)
             if channel_combinations is not None:
                 x = x[:, list(channel_combinations), :, :].clone()  # trainer.py:662-663
-            out = model(x, chunk_name, training_chunks, init_first_layer=init_first_layer, new_channel_init=new_channel_init)
+            if layers is None:
+                out = model(x, chunk_name, training_chunks, init_first_layer=init_first_layer, new_channel_init=new_channel_init)
+            else:
+                tok = model.feature_extractor.get_intermediate_layers(x, n=layers, chunk=chunk_name, training_chunks=training_chunks,
+                                                                      new_channel_init=new_channel_init, pool="channel")  # [b, 1 + C, D] each:
+                parts = [t[:, 0] for t in tok]                                                   # the tokens themselves are never written
+                if pool == "channel":
+                    parts.append(tok[-1][:, 1:].mean(dim=1))  # every channel has the same n_p: the mean of the channel means
+                out = torch.cat(parts, dim=-1)
             feats.append(out.float().cpu())
         folder = os.path.join(feature_dir, chunk_name)
         os.makedirs(folder, exist_ok=True)

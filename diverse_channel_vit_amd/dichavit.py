@@ -165,6 +165,29 @@ class _PickCounter(defaultdict):
     del _n, _make
 
 
+def _parse_layers(n, depth: int) -> List[int]:
+    """get_intermediate_layers' `n` -> block indices in block order: an int asks for the last n blocks, a sequence names blocks (negative counts
+    from the end).  ValueError for anything else, before any device work."""
+    if isinstance(n, bool):
+        raise ValueError(f"n={n!r}: expected an int or a sequence of block indices")
+    if isinstance(n, (int, np.integer)):
+        if not 1 <= int(n) <= depth:
+            raise ValueError(f"n={n}: expected 1 <= n <= {depth} (the encoder's depth)")
+        return list(range(depth - int(n), depth))
+    try:
+        idx = list(n)
+    except TypeError:
+        raise ValueError(f"n={n!r}: expected an int or a sequence of block indices") from None
+    if not idx or any(isinstance(i, bool) or not isinstance(i, (int, np.integer)) for i in idx):
+        raise ValueError(f"n={n!r}: expected a non-empty sequence of int block indices")
+    if any(not -depth <= int(i) < depth for i in idx):
+        raise ValueError(f"n={n!r}: block indices must lie in [-{depth}, {depth})")
+    blocks = sorted(int(i) % depth for i in idx)
+    if len(set(blocks)) != len(blocks):
+        raise ValueError(f"n={n!r}: duplicate block indices")
+    return blocks
+
+
 class _Holder(nn.Module):
     def forward(self, *a, **k):  # pragma: no cover
         raise RuntimeError("parameter container of the HIP path; call DiChaViT.forward")
@@ -287,6 +310,30 @@ class ChannelVisionTransformer(_Holder):
             raise RuntimeError("get_last_selfattention runs through the DiChaViT that owns this encoder (its parameter arena and operand "
                                "copies); this ChannelVisionTransformer is not linked to one")
         return owner._probe_attention(x, chunk, layer_idx, query_rows)
+
+    def get_intermediate_layers(self, x, extra_tokens={}, n=1, *, chunk="", training_chunks=None, new_channel_init=None, pool=None):
+        """models/dichavit.py:665-673 as it is meant: the token features of the last `n` blocks — for each of them the residual stream after that
+        block with the encoder's FINAL norm applied — as a list of fp32 tensors on x's device, detached (an inspection API: no gradient), earliest
+        block first.  The reference's own body raises TypeError on every call (it calls prepare_tokens(x, extra_tokens) with the wrong arity and has no
+        way to name the chunk); x, extra_tokens (accepted and ignored, as in get_last_selfattention) and n are its parameters, the rest are keyword-only
+        extensions.  The tokens are prepared as forward() prepares them (chunk looked up in the mapper, training_chunks / new_channel_init at eval,
+        HCS sampling, token drop and DropPath in train mode, the input affine).  Blocks after the last requested one do not run.
+
+        n: an int, 1 <= n <= depth, or a sequence of distinct block indices (negative counts from the end); entries come back in block order.
+        pool=None: each entry is [B, N, D] — every token the blocks saw, CLS first, token 1 + c * n_p + i = patch i of channel c (with token drop
+        in train mode: the kept tokens).
+        pool="channel": each entry is [B, 1 + C, D] — row 0 the normed CLS token, row 1 + c the mean over the n_p normed patch tokens of channel c,
+        channels in this forward's token order (the chunk's, or the HCS subset's); DINO's avgpool_patchtokens is the mean of rows 1 .. C.  One
+        pass of dcv_ln_pool_channels over the residual stream: the normed tokens are never written.  Raises ValueError under token drop (ragged
+        channel segments)."""
+        blocks = _parse_layers(n, len(self.blocks))
+        if pool not in (None, "channel"):
+            raise ValueError(f"pool={pool!r}: expected None or 'channel'")
+        owner = self._owner() if self._owner is not None else None
+        if owner is None:
+            raise RuntimeError("get_intermediate_layers runs through the DiChaViT that owns this encoder (its parameter arena and operand "
+                               "copies); this ChannelVisionTransformer is not linked to one")
+        return owner._probe_layers(x, chunk, training_chunks, new_channel_init, blocks, pool)
 
     @staticmethod
     def _init_weights(m):  # dichavit.py:509-516
@@ -779,11 +826,16 @@ class DiChaViT(nn.Module):
             out.append(tuple(pair))
         return out
 
-    def _run_forward(self, x, ch_idx_dev, C, E, pos_tab, want_ortho, save, keep=None, st_scale=None, st_shift=None, tok=None, probe=None):
+    def _run_forward(self, x, ch_idx_dev, C, E, pos_tab, want_ortho, save, keep=None, st_scale=None, st_shift=None, tok=None, probe=None,
+                     capture=None):
         """probe=(layer, rows): get_last_selfattention — run blocks < layer as the forward does, stop at block `layer` after its norm1 and qkv
         GEMM and return its attention probabilities [B, H, rows, N] (fp32) instead of the state.  Needs save=False and want_ortho=False.  The
         model's operand copies (_bf16, _bf16_t, _qbias) and _sr_seed are left alone — a training forward's backward may still read them — and
-        round-to-nearest straight copies are cast into scratch instead."""
+        round-to-nearest straight copies are cast into scratch instead.
+        capture=(blocks, pool): get_intermediate_layers — the same discipline; every block runs on all rows (no CLS-only tail), the final norm of
+        the stream after each block of `blocks` (ascending) is launched right after that block — with save=False the stream is updated in place,
+        so the capture is stream-ordered before the next block overwrites it — and the list of captures is returned after the last of them
+        instead of the state.  pool=None: [B, N, D] (dcv_ln_fwd, fp32 output); pool="channel": [B, 1 + C, D] (dcv_ln_pool_channels)."""
         fe = self.feature_extractor
         D, H = self.dim, fe.num_heads
         P = fe.patch_size
@@ -794,7 +846,7 @@ class DiChaViT(nn.Module):
         dev = x.device
         bf, f32 = torch.bfloat16, torch.float32
         ps = bool(self.attn_prescaled)  # pre-scaled q for this forward AND its backward (kept in the saved state)
-        if probe is None:
+        if probe is None and capture is None:
             self._refresh_operand_copies(stochastic=bool(save) and self.training and self.stochastic_weight_rounding, prescale_q=ps)
             wbuf, qbias = None, self._qbias
         else:
@@ -840,7 +892,7 @@ class DiChaViT(nn.Module):
             st.update(N=N, M=M)
         # --- encoder blocks ---
         scale = 64 ** -0.5
-        layers = []
+        layers, captured = [], []
         xcur = xs.view(M, D)
         final_stride = N * D
         drop = self._drop_path_scales(B, dev)
@@ -852,7 +904,7 @@ class DiChaViT(nn.Module):
         pre_ln = None
         for bi, blk in enumerate(fe.blocks):
             L = {}
-            tail = self.cls_only_tail and bi == len(fe.blocks) - 1
+            tail = self.cls_only_tail and bi == len(fe.blocks) - 1 and capture is None  # a captured last block runs on all rows
             dsc = drop[bi] if drop is not None else None  # (attention branch, MLP branch) factors [B] or None
             if pre_ln is not None:  # norm1 of this block came out of the previous block's fc2 + residual epilogue
                 u1, mean1, rstd1 = pre_ln
@@ -906,6 +958,9 @@ class DiChaViT(nn.Module):
             hact = torch.empty(R, 4 * D, dtype=bf, device=dev)
             hip.gemm_nt(u2, wb(blk.mlp.fc1.weight), hip.EPI_BIAS_GELU_BF16, z, bias=blk.mlp.fc1.bias, out2=hact)
             xout = torch.empty(R, D, dtype=f32, device=dev) if (save or tail) else xmid
+            # a capture that ends at this block keeps this launch although block bi + 1 never runs: the stream of block bi must come from the
+            # same kernel whether or not later blocks are requested (n=4 equals four single-index calls bit for bit), at the cost of one unused
+            # norm1 output in the epilogue
             nxt = fe.blocks[bi + 1] if bi + 1 < len(fe.blocks) else None
             if fuse_ln and not tail and nxt is not None:
                 # mlp.fc2 + residual AND the NEXT block's norm1 (its full rows are needed even when that block is the CLS-only tail: keys and values)
@@ -923,6 +978,16 @@ class DiChaViT(nn.Module):
                          rstd2=rstd2, z=z, h=hact, tail=tail, o_c=o_c)
                 layers.append(L)
             xcur = xout
+            if capture is not None and bi in capture[0]:
+                if capture[1] == "channel":
+                    cap = torch.empty(B, 1 + C, D, dtype=f32, device=dev)
+                    hip.ln_pool_channels(xcur, fe.norm.weight, fe.norm.bias, cap, B, C, n, D, LN_EPS)
+                else:
+                    cap = torch.empty(B, N, D, dtype=f32, device=dev)
+                    hip.ln_fwd(xcur, fe.norm.weight, fe.norm.bias, cap, None, None, M, D, LN_EPS)
+                captured.append(cap)
+                if bi == capture[0][-1]:
+                    return captured
             if tail:
                 final_stride = D  # the last block handed over compact CLS rows
         # --- final LayerNorm on the CLS rows only (dichavit.py:651-652) ---
@@ -1365,6 +1430,18 @@ class DiChaViT(nn.Module):
                 raise ValueError(f"query_rows={query_rows}: expected 1 <= query_rows <= {N} (the tokens this block sees)")
             return self._run_forward(tk.x, tk.ch_idx_dev, tk.C, tk.E_tok, tk.pos_tab, False, save=False, keep=tk.keep, st_scale=tk.scale,
                                      st_shift=tk.shift, tok=tk.tok, probe=(layer_idx % depth, rows))
+
+    def _probe_layers(self, x, chunk_name, training_chunks, new_channel_init, blocks, pool):
+        """ChannelVisionTransformer.get_intermediate_layers: the tokens as forward() prepares them, then blocks 0 .. blocks[-1] through
+        _run_forward's capture.  DataParallel's begin_forward() is not called: no gradient leaves this path."""
+        with torch.autocast(device_type="cuda", enabled=False), torch.no_grad():
+            self._check_input(x)
+            tk = self._prepare_tokens(x, chunk_name, training_chunks, new_channel_init)
+            if pool == "channel" and tk.keep is not None:
+                raise ValueError("pool='channel' needs every channel's n_p patch tokens: with dropout_tokens_hcs active in train mode the channel "
+                                 "segments are ragged (pool=None returns the kept tokens)")
+            return self._run_forward(tk.x, tk.ch_idx_dev, tk.C, tk.E_tok, tk.pos_tab, False, save=False, keep=tk.keep, st_scale=tk.scale,
+                                     st_shift=tk.shift, tok=tk.tok, capture=(blocks, pool))
 
     def _ortho_from_stats(self, stats, C, n):
         """loss_fn.py:44-59 on the per-image (pos_sum, neg_sum)."""

@@ -31,6 +31,8 @@ _SIGS = {
     "dcv_gemm_tn_group_ws_floats": ([_vp, _i, _i], _l),
     "dcv_gemm_tn_group": ([_vp, _i, _i, _vp, _l, _vp], _i),
     "dcv_ln_fwd": ([_vp, _l, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _f, _vp], _i),
+    "dcv_ln_pool_channels_ws_floats": ([_i, _i, _i, _i], _l),
+    "dcv_ln_pool_channels": ([_vp, _vp, _vp, _f, _vp, _i, _i, _i, _i, _vp, _l, _vp], _i),
     "dcv_ln_bwd": ([_vp, _i, _vp, _l, _vp, _vp, _vp, _vp, _vp, _l, _vp, _vp, _vp, _i, _i, _vp], _i),
     "dcv_ln_bwd_det_ws_floats": ([_i, _i], _l),
     "dcv_ln_bwd_det": ([_vp, _i, _vp, _l, _vp, _vp, _vp, _vp, _vp, _l, _vp, _vp, _vp, _i, _i, _vp, _l, _vp], _i),
@@ -336,6 +338,24 @@ def ln_fwd(x, gamma, beta, out, mean, rstd, M, D, eps, x_row_stride=None):
         rc = load().dcv_ln_fwd(_p(x), D if x_row_stride is None else x_row_stride, _p(gamma), _p(beta), _p(out),
                                1 if out.dtype == torch.float32 else 0, _p(mean), _p(rstd), M, D, eps, _stream())
     _check(rc, "dcv_ln_fwd")
+
+
+def ln_pool_channels(x, gamma, beta, out, B, C, n_p, D, eps, ws=None):
+    """out [B, 1 + C, D] fp32 = LayerNorm of x [B, 1 + C * n_p, D] pooled per channel: row 0 the normed CLS row, row 1 + c the mean of the normed
+    patch rows of channel c (include/dcv.h: dcv_ln_pool_channels).  ws: the caller's workspace (tests); by default the stream's shared one."""
+    _req(x, torch.float32, "x"); _req(gamma, torch.float32, "gamma"); _req(beta, torch.float32, "beta"); _req(out, torch.float32, "out")
+    if x.numel() < B * (1 + C * n_p) * D or out.numel() < B * (1 + C) * D or gamma.numel() < D or beta.numel() < D:
+        raise ValueError("ln_pool_channels: x holds B*(1+C*n_p)*D floats, out B*(1+C)*D, gamma and beta D")
+    lib = load()
+    with _timer(lambda: (f"ln_pool_kernel<{2 if D <= 512 else 4}>", f"B{B} C{C} n{n_p} D{D}", 0.0, None, 4.0 * D * B * (2 + C * n_p + C))):
+        if ws is None:
+            need = _ws_size(lib.dcv_ln_pool_channels_ws_floats(B, C, n_p, D))
+            ws = _workspace(need, out) if need else None
+        else:
+            _req(ws, torch.float32, "ws")
+        rc = lib.dcv_ln_pool_channels(_p(x), _p(gamma), _p(beta), float(eps), _p(out), B, C, n_p, D, _p(ws), ws.numel() if ws is not None else 0,
+                                      _stream())
+    _check(rc, "dcv_ln_pool_channels")
 
 
 def ln_bwd(du, x, mean, rstd, gamma, dx_in, dx_out, dx_bf16, dgamma, dbeta, M, D, x_row_stride=None, dx_row_stride=None,

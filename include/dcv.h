@@ -118,6 +118,16 @@ int dcv_ln_fwd(const float* x, long x_row_stride, const float* gamma, const floa
 int dcv_ln_bwd(const void* du, int du_is_f32, const float* x, long x_row_stride, const float* mean, const float* rstd,
                const float* gamma, const float* dx_in, float* dx_out, long dx_row_stride, void* dx_bf16, float* dgamma,
                float* dbeta, int M, int D, void* stream);
+/* LayerNorm of a token stream pooled per input channel (ChannelVisionTransformer.get_intermediate_layers, pool="channel"):
+ * x f32 [B, N, D] with N = 1 + C * n_p, rows D floats apart (CLS, then the n_p patch tokens of channel 0, 1, ...) ->
+ * out f32 [B, 1 + C, D]: row 0 = LN(x[b, 0]) (bit-identical to dcv_ln_fwd's f32 output of that row), row 1 + c = the mean over the n_p
+ * rows of channel c of LN(row); gamma / beta are applied once, to the mean of the normalised rows.  Reads x once, never writes the normed
+ * tokens.  No atomics, and every summation order is a function of (B, C, n_p, D) alone: bitwise reproducible.  ws: at least
+ * dcv_ln_pool_channels_ws_floats(B, C, n_p, D) floats (0 when B * C segments fill the chip: ws may then be NULL), contents irrelevant.
+ * D % 4 == 0, D <= 1024 and ws_floats large enough, else DCV_ERR_SHAPE; every pointer 16-byte aligned, else DCV_ERR_ALIGN. */
+long dcv_ln_pool_channels_ws_floats(int B, int C, int n_p, int D);
+int dcv_ln_pool_channels(const float* x, const float* gamma, const float* beta, float eps, float* out, int B, int C, int n_p, int D,
+                         float* ws, long ws_floats, void* stream);
 
 /* DETERMINISTIC forms of the other entries that combine partial sums of several workgroups (LayerNorm's dgamma / dbeta, the tokeniser's
  * d(channel_embed) / d(pos), the diversity loss' per-channel sums, the gradient norm): partials go through `ws` (at least *_det_ws_floats
