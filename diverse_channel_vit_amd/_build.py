@@ -17,8 +17,7 @@ EXTRA = {"attn.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
          # (dK/dV kernel 4 % slower); the forward keeps it (its packed forms are written out and measured 2 % faster)
          "attn_bwd.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1", "-fno-slp-vectorize"],
          # third dK/dV form: its MFMAs are inline asm with explicit register classes; the flag keeps hipcc's own choices out of the accumulator file
-         "attn_bwd3.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1", "-fno-slp-vectorize"],
-         "attn_bwd3q.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1", "-fno-slp-vectorize"]}
+         "attn_bwd3.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1", "-fno-slp-vectorize"]}
 
 
 def sources():
@@ -32,17 +31,15 @@ def _stale(target, deps):
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-#: diagnostic translation units that REPLACE a product source in a variant build: the stamp / ablation / wrap / stagger harness of the GEMM kernels
-#: lives in tools/probes/gemm_instrumented.hip (the shipped csrc/gemm.hip carries none of it: VERDICT r3 item 8)
-INSTRUMENTED = {"gemm.hip": os.path.join(HERE, "..", "tools", "probes", "gemm_instrumented.hip"),
-                "attn.hip": os.path.join(HERE, "..", "tools", "probes", "attn_instrumented.hip"),
-                "attn_bwd.hip": os.path.join(HERE, "..", "tools", "probes", "attn_bwd_instrumented.hip"),
-                "attn_bwd3.hip": os.path.join(HERE, "..", "tools", "probes", "attn_bwd3_instrumented.hip")}  # -DDCV_K3_ABL=<mask>: timing-only ablations of the persistent dK/dV kernel  # -DDCV_FABL=<mask>: forward-loop ablations
+#: diagnostic translation units that REPLACE a product source in a variant build.  A twin is kept only while it builds and the resulting library still
+#: carries every entry of hip.EXPORTS; the one left holds the -DDCV_K3_ABL=<mask> timing-only ablations and the -DDCV_K3_STAMP cycle stamps of the
+#: persistent dK/dV kernel (the twins of gemm.hip, attn.hip and attn_bwd.hip had fallen behind the product sources and were removed)
+INSTRUMENTED = {"attn_bwd3.hip": os.path.join(HERE, "..", "tools", "probes", "attn_bwd3_instrumented.hip")}
 
 
 def build_variant(name: str, defines, verbose: bool = True, flags=(), instrumented=()) -> str:
     """A/B build of the same ABI with extra -D flags -> libdcv_hip_<name>.so (select it with DCV_LIB=...).
-    instrumented: product sources to replace by their diagnostic twin (INSTRUMENTED), e.g. ("gemm.hip",) for -DDCV_STAMP=1 / -DDCV_GABL=n."""
+    instrumented: product sources to replace by their diagnostic twin (INSTRUMENTED), e.g. ("attn_bwd3.hip",) for -DDCV_K3_ABL=n."""
     objdir = os.path.join(HERE, "build", "variant_" + name)
     os.makedirs(objdir, exist_ok=True)
     objs = []

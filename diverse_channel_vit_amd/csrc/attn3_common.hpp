@@ -1,4 +1,4 @@
-// Shared pieces of the one-wave-per-SIMD attention backward kernels (attn_bwd3.hip: dK / dV; attn_bwd3q.hip: dQ): inline-asm MFMAs with explicit
+// Helpers of the one-wave-per-SIMD dK / dV attention backward kernel (attn_bwd3.hip): inline-asm MFMAs with explicit
 // register classes, the scheduling fence and the value pin, bf16 packing.  See attn_bwd3.hip for the design and the hazard rules.
 #pragma once
 #include "attn_common.hpp"

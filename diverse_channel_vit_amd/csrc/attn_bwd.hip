@@ -465,9 +465,6 @@ static int dq_launch(const void* qkv, const void* o, const void* dO, const float
     if (!dqkv) return DCV_ERR_NULL;
     if (Nq < 1 || Nq > N) return DCV_ERR_SHAPE;
     AttnArgs a{(const bf16_t*)qkv, (bf16_t*)o, (const bf16_t*)dO, (float*)lse, ws, (bf16_t*)dqkv, B, N, H, scale, Nq};
-#if DCV_DQ_FORM == 3
-    if (ps && Nq == N) return dcv_dq3_launch(qkv, o, dO, lse, ws, dqkv, B, N, H, scale, (hipStream_t)stream);  // attn_bwd3q.hip (round 5); same sums, same order
-#endif
     const dim3 grid(B * H * ((N + 127) / 128));
     if (ps) hipLaunchKernelGGL(attn_bwd_dq2_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, a);
     else hipLaunchKernelGGL(attn_bwd_dq2_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, a);
@@ -490,18 +487,6 @@ static int dkdv_launch(const void* qkv, const void* dO, const float* lse, const 
     DCV_LAUNCH_CHECK();
     return DCV_OK;
 }
-
-#if DCV_DQ_FORM == 3
-__attribute__((visibility("hidden"))) int dcv_dq2_range(const void* qkv, const void* o, const void* dO, const float* lse, float* ws, void* dqkv, int B, int N, int H, float scale,
-                                                        int row_lo, hipStream_t stream) {
-    AttnArgs a{(const bf16_t*)qkv, (bf16_t*)o, (const bf16_t*)dO, (float*)lse, ws, (bf16_t*)dqkv, B, N, H, scale, N};
-    a.key_lo = row_lo;  // for the dQ kernel the range is one of query rows
-    hipLaunchKernelGGL(attn_bwd_dq2_kernel<true>, dim3(B * H * ((N - row_lo + 127) / 128)), dim3(256), 0, stream, a);
-    DCV_LAUNCH_CHECK();
-    return DCV_OK;
-}
-
-#endif
 
 __attribute__((visibility("hidden"))) int dcv_dkdv2_range(const void* qkv, const void* dO, const float* lse, const float* ws, void* dqkv, int B, int N, int Nq, int H, float scale, int key_lo,
                     hipStream_t stream) {

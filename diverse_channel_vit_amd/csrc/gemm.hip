@@ -555,20 +555,6 @@ __device__ __forceinline__ void np_issue(const NpTile& t, int kt, unsigned stage
     for (int q = 0; q < 4; ++q) glds16(t.gW[q] + kt * NP_BK, stage_base + dmaW + q * 1024);
 }
 
-// Round 5: the two co-resident workgroups of a CU start at the same instant on identical work, so both sit in the k-loop, then
-// both in the epilogue: no overlap by construction.  -DDCV_PAIR_OFFSET=<cycles> (variant builds; 0 in the product) delays, once, the workgroup
-// whose waves got the SECOND wave slot of their SIMD (HW_ID.wave_id != 0) before its first stage; -DDCV_PAIR_STAMP records the cycle at which each
-// of a workgroup's first 24 epilogues starts, with the CU it runs on (tools/gemm_pair_phase.py checks that the pair stays out of phase).
-#ifndef DCV_PAIR_OFFSET
-#define DCV_PAIR_OFFSET 0
-#endif
-#ifdef DCV_PAIR_STAMP
-__device__ unsigned long long np_stamps[1024 * 32];
-extern "C" int dcv_pair_stamps(void* host_dst, size_t bytes) {
-    return hipMemcpyFromSymbol(host_dst, HIP_SYMBOL(np_stamps), bytes < sizeof(np_stamps) ? bytes : sizeof(np_stamps)) == hipSuccess ? 0 : 1;
-}
-#endif
-
 template <int EPI>
 __global__ __launch_bounds__(256) void gemm_nt_pair_kernel(GemmNtArgs a) {
     __shared__ __attribute__((aligned(16))) char smem[NP_SMEM];
@@ -596,21 +582,6 @@ __global__ __launch_bounds__(256) void gemm_nt_pair_kernel(GemmNtArgs a) {
     NpTile cur, nxt;
     np_tile_setup(a, L, tiles_n, wave, lane, cur);
     int g = 0;  // global stage counter: stage g lives in buffer g & 1
-#if DCV_PAIR_OFFSET || defined(DCV_PAIR_STAMP)
-    const unsigned hw_id = __builtin_amdgcn_s_getreg((15 << 11) | 4);       // HW_REG_HW_ID[15:0]: wave_id 3:0, simd 5:4, pipe 7:6, cu 11:8, sh 12, se 15:13
-    const unsigned xcc_id = __builtin_amdgcn_s_getreg((3 << 11) | 20) & 15;  // HW_REG_XCC_ID[3:0]
-    const bool second = (hw_id & 15) != 0;
-#endif
-#if DCV_PAIR_OFFSET
-    if (second) {
-        const unsigned long long t0 = __builtin_amdgcn_s_memtime();
-        while (__builtin_amdgcn_s_memtime() - t0 < (unsigned long long)DCV_PAIR_OFFSET) __builtin_amdgcn_s_sleep(16);
-    }
-#endif
-#ifdef DCV_PAIR_STAMP
-    int n_epi = 0;
-    if (tid == 0 && blockIdx.x < 1024) np_stamps[blockIdx.x * 32] = ((unsigned long long)xcc_id << 32) | hw_id;
-#endif
     np_issue(cur, 0, smem_base, dmaA, dmaW);
     bool stores_behind = false;  // the previous tile's S epilogue stores were issued after this tile's first stage
     float bz[8], bz_next[8];
@@ -656,10 +627,6 @@ __global__ __launch_bounds__(256) void gemm_nt_pair_kernel(GemmNtArgs a) {
         const bool has_next = Ln >= 0;
         Lnext = (has_next && Ln + G < total) ? Ln + G : -1;
         const bool full = (cur.m0 + NP_BM <= a.M) && (cur.n0 + NP_BN <= a.N);
-#ifdef DCV_PAIR_STAMP
-        if (tid == 0 && blockIdx.x < 1024 && n_epi < 24) np_stamps[blockIdx.x * 32 + 1 + n_epi] = __builtin_amdgcn_s_memtime();
-        ++n_epi;
-#endif
         nt_epilogue_block<EPI, 4, 4, 4, 0>(a, acc, cur.m0 + wm * 64, cur.n0 + wn * 64, r16, kg, bz, [&]() {
             if (has_next) {
                 np_tile_setup(a, Ln, tiles_n, wave, lane, nxt);
@@ -1205,176 +1172,6 @@ __global__ __launch_bounds__(64 * WS_WAVES) void gemm_nt_ws_kernel(GemmNtArgs a)
 }
 #endif  // DCV_NT_WS
 
-#ifndef DCV_NT_ALT
-#define DCV_NT_ALT 0
-#endif
-#if DCV_NT_ALT
-// ------------------------------------------------------------------------------------------------
-// gemm_nt_alt (round 5, DCV_TILE_ALT; variant builds with -DDCV_NT_ALT=1 only — measured 15-27 % SLOWER than the best shipped tile on every shape,
-// profiles/r05_x9_*): the 256 x 384 kernel's eight waves as TWO groups of four (one wave of either group on every SIMD) that work on the
-// two 192-column halves of a tile in ALTERNATING phases: while group 0 runs the k-loop of its half (the matrix pipe), group 1 runs the epilogue of the half it
-// accumulated one phase earlier (vector arithmetic, auxiliary loads, stores), then they swap.  The LDS ring belongs to whichever group is in its k-loop — two
-// stages of (256 + 192) rows x 128 B = 112 KB — so, unlike two co-resident workgroups (gemm_nt_pair: 128 x 128 tiles), the wave tile stays 64 x 192.  A phase is
-// K / 64 slots; every slot opens with the workgroup barrier (the k-loop group needs it per stage, the other group just arrives), the epilogue group spreads its
-// six chunks (2 row blocks x one 64-column group each) over the slots and issues the first stage of ITS next half into the free buffer during the last slot.
-// Cost: the A panel is pulled into LDS once per half (3840 -> 5376 lines per tile at K = 384).  bf16-output epilogues only.
-constexpr int NA_A_BYTES = 256 * 128, NA_W_BYTES = 192 * 128, NA_STAGE_BYTES = NA_A_BYTES + NA_W_BYTES, NA_SMEM = 2 * NA_STAGE_BYTES;  // 56 KB stages, 112 KB
-
-template <int EPI>
-__global__ __launch_bounds__(512) void gemm_nt_alt_kernel(GemmNtArgs a) {
-    __shared__ __attribute__((aligned(16))) char smem[NA_SMEM];
-    static_assert(!epi_f32out<EPI>() && EPI != DCV_EPI_RESID_LN, "bf16-output epilogues only");
-    constexpr bool HAS_BIAS = (EPI != DCV_EPI_PLAIN_BF16) && (EPI != DCV_EPI_GELU_BWD_BF16);
-    constexpr bool HAS_AUX = (EPI == DCV_EPI_GELU_BWD_BF16);
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int grp = wave >> 2, wm = wave & 3;  // waves w and w + 4 share a SIMD: one of either group
-    const int tiles_n = a.N / N3_BN;
-    const int tiles_m = (a.M + N3_BM - 1) / N3_BM;
-    const int total = tiles_m * tiles_n;
-    const int G = gridDim.x;
-    const int pos = ((G & 7) == 0) ? (blockIdx.x & 7) * (G >> 3) + (blockIdx.x >> 3) : blockIdx.x;
-    if (pos >= total) return;
-    const int n_mine = (total - pos + G - 1) / G;  // tiles this workgroup walks: pos, pos + G, ...
-
-    const unsigned smem_base = __builtin_amdgcn_readfirstlane(lds_addr(smem));
-    const unsigned dmaA = 64 * wm * 128, dmaW = NA_A_BYTES + 48 * wm * 128;  // per stage a k-loop wave brings A rows [64 wm, +64) = 8 pieces, W rows [48 wm, +48) = 6
-    const int nk = a.K / N3_BK;
-    const int r16 = lane & 15, kg = lane >> 4;
-    int fA0, fA1, fW0, fW1;
-    {
-        const int rowA = (wm * 64 + r16) * 128, rowW = NA_A_BYTES + r16 * 128;
-        const int co0 = (kg ^ swz64n(r16)) << 4;
-        fA0 = rowA + co0; fA1 = rowA + (co0 ^ 64); fW0 = rowW + co0; fW1 = rowW + (co0 ^ 64);
-        asm volatile("" : "+v"(fA0), "+v"(fA1), "+v"(fW0), "+v"(fW1));
-    }
-    unsigned voffA[2], voffW[2];
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        const int rowa = 64 * wm + 8 * q + (lane >> 3), roww = 48 * wm + 8 * q + (lane >> 3);
-        voffA[q] = (unsigned)(((size_t)rowa * a.lda + (((lane & 7) ^ swz64n(rowa)) * 8)) * 2);
-        voffW[q] = (unsigned)(((size_t)roww * a.ldw + (((lane & 7) ^ swz64n(roww)) * 8)) * 2);
-    }
-    // stage kt of the half (tile L, column half grp) into the buffer at stage_base
-    auto issue = [&](int L, int kt, unsigned stage_base) {
-        const int m0 = __builtin_amdgcn_readfirstlane((L / tiles_n) * N3_BM), n0 = __builtin_amdgcn_readfirstlane((L % tiles_n) * N3_BN + 192 * grp);
-        const bf16_t* ab = a.A + (size_t)m0 * a.lda + kt * N3_BK;
-        const bf16_t* wb = a.W + (size_t)n0 * a.ldw + kt * N3_BK;
-        if (m0 + N3_BM <= a.M) {
-#pragma unroll
-            for (int q = 0; q < 8; ++q) glds16s(ab + (size_t)(q >> 1) * 16 * a.lda, voffA[q & 1], stage_base + dmaA + q * 1024);
-        } else {
-            int ln = lane;
-            asm volatile("" : "+v"(ln));
-#pragma unroll
-            for (int q = 0; q < 8; ++q) {
-                const int row = 64 * wm + 8 * q + (ln >> 3);
-                const int rc = min(m0 + row, a.M - 1) - m0;
-                glds16s(ab, (unsigned)(((size_t)rc * a.lda + (((ln & 7) ^ swz64n(row)) * 8)) * 2), stage_base + dmaA + q * 1024);
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < 6; ++q) glds16s(wb + (size_t)(q >> 1) * 16 * a.ldw, voffW[q & 1], stage_base + dmaW + q * 1024);
-    };
-
-    int g = 0;  // slot counter of the workgroup: the k-loop group's stage of slot g lives in buffer g & 1
-    // a phase in which this group has nothing in its accumulators: arrive at every slot's barrier; with_issue: my first stage goes out in the last slot
-    auto idle_phase = [&](bool with_issue) {
-        for (int kt = 0; kt < nk; ++kt, ++g) {
-            __builtin_amdgcn_s_barrier();
-            if (with_issue && kt == nk - 1) issue(pos, 0, smem_base + ((g + 1) & 1) * NA_STAGE_BYTES);
-        }
-    };
-    // group 0: k e k e ... k e idle;  group 1: idle k e ... k e — in every phase one group owns the ring and the matrix pipe, the other stores.  The loop body is
-    // straight-line (k-loop, then epilogue): the accumulators are defined and dead inside one iteration (as a branch per phase they became loop-carried values
-    // the register allocator spilled)
-    if (grp == 0) issue(pos, 0, smem_base);
-    else idle_phase(true);
-
-    for (int t = 0; t < n_mine; ++t) {
-        const int L = pos + t * G;
-        f32x4 acc[4][12];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 12; ++j)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) acc[i][j][r] = 0.f;
-#pragma clang loop unroll(disable)
-        for (int kt = 0; kt < nk; ++kt, ++g) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // my pieces of stage kt (and, for kt == 0, my last epilogue's stores)
-            __builtin_amdgcn_s_barrier();
-            const char* st = smem + (g & 1) * NA_STAGE_BYTES;
-            const char* const pA0 = st + fA0;
-            const char* const pA1 = st + fA1;
-            const char* const pW0 = st + fW0;
-            const char* const pW1 = st + fW1;
-            auto rdW = [&](int s2) { return as_bf16x8(lds_read128(s2 >= 12 ? pW1 : pW0, (s2 % 12) * 16 * 128)); };
-            bf16x8 af[4], wq[3];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) af[i] = as_bf16x8(lds_read128(pA0, i * 16 * 128));
-            wq[0] = rdW(0);
-            wq[1] = rdW(1);
-            __builtin_amdgcn_sched_barrier(0);
-            if (kt + 1 < nk) issue(L, kt + 1, smem_base + ((g + 1) & 1) * NA_STAGE_BYTES);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int s2 = 0; s2 < 24; ++s2) {
-                if (s2 + 2 < 24) wq[(s2 + 2) % 3] = rdW(s2 + 2);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    acc[i][s2 % 12] = mfma16(wq[s2 % 3], af[i], acc[i][s2 % 12]);
-                    if (s2 == 11) af[i] = as_bf16x8(lds_read128(pA1, i * 16 * 128));
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-        // ---- epilogue phase: six chunks (one 64-column group x two 16-row blocks each) spread over the slots; my next first stage in the last slot ----
-        const int m_w = (L / tiles_n) * N3_BM + wm * 64, n_w = (L % tiles_n) * N3_BN + 192 * grp;
-        int ln = lane;
-        asm volatile("" : "+v"(ln));
-        const int r16e = ln & 15, kge = ln >> 4;
-        const int rr = r16e & 7, cl = 32 * (r16e >> 3) + 16 * (kge & 1) + 8 * (kge >> 1);
-        const bool more = t + 1 < n_mine;
-        // chunk ch runs in slot ch * nk / 6; the sequence over the chunks is straight-line (the accumulators of a chunk die with it), the slots between them
-        // are opened by a counted loop of barriers
-        int kt = 0;
-        auto open_slots = [&](int upto) {  // open slots kt .. upto (inclusive)
-            for (; kt <= upto; ++kt, ++g) {
-                __builtin_amdgcn_s_barrier();
-                if (more && kt == nk - 1) issue(L + G, 0, smem_base + ((g + 1) & 1) * NA_STAGE_BYTES);  // free since the barrier above
-            }
-        };
-#pragma unroll
-        for (int ch = 0; ch < 6; ++ch) {
-            open_slots(ch * nk / 6);
-            const int c = ch >> 1;
-            float bz[8];
-            if constexpr (HAS_BIAS) nt_load_bias<EPI, 4>(a, n_w + 64 * c, r16e, kge, bz);
-#pragma unroll
-            for (int ii = 0; ii < 2; ++ii) {
-                const int i = 2 * (ch & 1) + ii;
-                float x[2][8];
-                if constexpr (HAS_AUX) {
-#pragma unroll
-                    for (int h = 0; h < 2; ++h) epi_aux8<EPI>(a, min(m_w + 16 * i + 8 * h + rr, a.M - 1), min(n_w + 64 * c + cl, a.N - 8), x[h]);
-                }
-                float v0[8], v1[8], va[8], vb[8];
-                swap_pair8(acc[i][4 * c], acc[i][4 * c + 1], v0);
-                swap_pair8(acc[i][4 * c + 2], acc[i][4 * c + 3], v1);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) xchg_rows8(v0[e], v1[e], va[e], vb[e]);
-                const int m = m_w + 16 * i + rr, n = n_w + 64 * c + cl;
-                if (m < a.M && n < a.N) epi_store8<EPI>(a, m, n, va, x[0], bz);
-                if (m + 8 < a.M && n < a.N) epi_store8<EPI>(a, m + 8, n, vb, x[1], bz);
-            }
-        }
-        open_slots(nk - 1);
-    }
-    if (grp == 0) idle_phase(false);
-}
-#endif  // DCV_NT_ALT
-
 // ------------------------------------------------------------------------------------------------
 struct GemmTnArgs {
     const bf16_t* Y;
@@ -1389,8 +1186,6 @@ struct GemmTnArgs {
     float* part;       // deterministic mode: split s stores its partial tile to part[s * part_stride + p * Q + q] (and its bias partial to
     long part_stride;  // part[s * part_stride + P * Q + p]) with plain stores instead of adding atomically; det_reduce_kernel sums them
     long bias_off;     // gemm_tn384, deterministic mode: float offset in `part` of the bias partials [splits * tiles_q][P]
-    int mode;          // grouped launch only: 0 = 384 x 128 tiles; 1 = 384 x 256 tiles; 2 = 384 x 256 tiles of the TRANSPOSED product (Y and X exchanged by
-                       // the launcher: P, Q, ldy, ldx are the exchanged ones; dW / part / dbias keep the caller's layout: element (p, q) at q * P + p)
 };
 
 __global__ __launch_bounds__(256) void gemm_tn_kernel(GemmTnArgs a) {
@@ -1686,195 +1481,6 @@ __device__ __forceinline__ void tn384_body(const GemmTnArgs& a, int bid, char* s
     }
 }
 
-#ifndef DCV_TN_WIDE_Q
-#define DCV_TN_WIDE_Q 0  // variant builds: bit 0: 384 x 256 tiles for products with Q % 256 == 0; bit 1: for the transposed product (measured: +3 % / +12 % SLOWER, profiles/r05_x5_*); bit 2: 384 x 192 tiles for Q % 192 == 0
-#endif
-#if DCV_TN_WIDE_Q
-// ------------------------------------------------------------------------------------------------
-// gemm_tn384w (round 5): the same loop on a 384 (P) x 256 (Q) tile — 154 FLOP per operand byte pulled L2 -> LDS instead of 96.  Why: the 384 x 128 kernel
-// waits for operand delivery (MFMA busy 0.39; TCP_PENDING_STALL 49 % of the launch; 28.9 M 128-byte requests at 457 cycles each = 59 in flight per CU
-// by Little's law, 37 % of them compulsory HBM misses: profiles/r05_x5_*): the vector-memory path of a CU holds a fixed number of requests and every
-// one takes an HBM latency, so the lever is requests per FLOP.  8 waves as 4 (P) x 2 (Q), each 96 x 128 = 3 x 4 MFMA tiles (192 accumulators, two waves
-// per SIMD); a stage is five [32 rows][128 cols] images (40 KB), four stages = the whole LDS; five DMA pieces per wave and stage.
-// SWAP: the launcher exchanged Y and X (a product whose Q is 384 and whose P is a multiple of 256, e.g. fc1's 1536 x 384): the tile is one of the
-// transposed product, stored transposed (four consecutive p per lane: 16-byte stores at a row stride), and the bias gradient — the column sums of
-// the caller's Y — comes from the X images.
-constexpr int T3W_STAGES = 4, T3W_STAGE_BYTES = 5 * T3_IMG;  // 160 KB
-// NJ = 3: a 384 x 192 tile on the same five images (waves 96 x 96 = 3 x 3 MFMA tiles, 144 accumulators; 128 FLOP per operand byte): every product of the model has
-// Q % 192 == 0.  The fifth image then holds X columns 128-191 only; its DMA lanes whose slot lies in the unused half fetch the used half's lines again (no new request).
-template <bool SWAP, int NJ = 4>
-__device__ __forceinline__ void tn384w_body(const GemmTnArgs& a, int bid, char* smem) {
-    static_assert(NJ == 4 || (NJ == 3 && !SWAP), "tile widths");
-    constexpr int QT = 64 * NJ;  // tile width
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wp = wave >> 1, wq = wave & 1;
-    const int h = lane >> 5, r32 = lane & 31, li = lane & 15, g1 = (lane >> 4) & 1;
-    const int tiles_q = a.Q / QT, tiles = tiles_q * (a.P / 384);
-    const int split = bid / tiles;
-    bid -= split * tiles;
-    const int tq = bid % tiles_q, tp = bid / tiles_q;
-    const int p0 = tp * 384, q0 = tq * QT;
-    const int m_begin = split * a.m_per_split;
-    const int m_end = min(a.M, m_begin + a.m_per_split);
-    if (m_begin >= m_end) return;
-    const int nk = (m_end - m_begin + T3_BK - 1) / T3_BK;
-    const int last_valid = (m_end - m_begin) - (nk - 1) * T3_BK;
-
-    // DMA: piece p = 5 wave + j (j = 0..4) of the stage's 40: image p >> 3 (0-2: Y columns p0 + 128 image; 3, 4: X columns q0 + 128 (image - 3)), rows
-    // 4 (p & 7) .. + 3; lane -> row lane >> 4 of the four, physical chunk lane & 15 (the row's swizzle depends on row & 3 = lane >> 4 only)
-    const int lrow = lane >> 4, pc = lane & 15;
-    const int lcol = ((((pc >> 2) ^ (lrow & 3)) << 2) | (pc & 3)) * 8;
-    const unsigned smem_base = __builtin_amdgcn_readfirstlane(lds_addr(smem));
-    const bf16_t* gsrc[5];
-    int gld[5], grow[5];
-    unsigned gdst[5];
-#pragma unroll
-    for (int j = 0; j < 5; ++j) {
-        const int p = 5 * wave + j, img = p >> 3, rg = p & 7;
-        gsrc[j] = (img < 3 ? a.Y + p0 + 128 * img : a.X + q0 + 128 * (img - 3)) + ((NJ == 3 && img == 4) ? (lcol & 63) : lcol);
-        gld[j] = img < 3 ? a.ldy : a.ldx;
-        grow[j] = 4 * rg + lrow;
-        gdst[j] = img * T3_IMG + rg * 1024;
-    }
-#define T3W_ISSUE(kt_)                                                                                    \
-    {                                                                                                     \
-        const unsigned sb_ = smem_base + ((kt_) % T3W_STAGES) * T3W_STAGE_BYTES;                          \
-        _Pragma("unroll") for (int j = 0; j < 5; ++j) {                                                   \
-            const int m_ = min(m_begin + (kt_) * T3_BK + grow[j], m_end - 1); /* tail rows: zeroed in LDS below */ \
-            glds16(gsrc[j] + (size_t)m_ * gld[j], sb_ + gdst[j]);                                         \
-        }                                                                                                 \
-    }
-    for (int st = 0; st < T3W_STAGES - 1; ++st)
-        if (st < nk) T3W_ISSUE(st)
-
-    f32x16 acc[3][NJ];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < NJ; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-    const int trow = 8 * h + (li >> 2);
-    int offA[3], offB[NJ];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const int c = 96 * wp + 32 * i + 16 * g1 + 4 * (li & 3);
-        offA[i] = (c >> 7) * T3_IMG + (c & 127);
-    }
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-        const int c = 32 * NJ * wq + 32 * j + 16 * g1 + 4 * (li & 3);
-        offB[j] = (3 + (c >> 7)) * T3_IMG + (c & 127);
-    }
-    auto tr_off = [](int imgcol, int row) {
-        const int base = imgcol & ~127, col = imgcol & 127;
-        return base + lds128_off(row, col);
-    };
-
-    // bias gradient = column sums of the caller's Y: !SWAP: the three Y images (48 column chunks x 10 row groups), paced over the tiles of a row
-    // as in tn384_body; SWAP: the two X images (32 chunks x 16 row groups), by the first tile row only (every tile row sees the same X columns)
-    const bool do_bias = (a.dbias != nullptr) && (!SWAP || tp == 0);
-    constexpr int BCH = SWAP ? 32 : 48, BRG = SWAP ? 16 : 10;
-    const int bch = tid % BCH, brg = tid / BCH;
-    float bs[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) bs[e] = 0.f;
-
-    for (int kt = 0; kt < nk; ++kt) {
-        const int rem = nk - 1 - kt;  // younger stages in flight: min(rem, 2), 5 DMA pieces per wave each
-        if (rem >= 2) asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
-        else if (rem == 1) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        if (kt + T3W_STAGES - 1 < nk) T3W_ISSUE(kt + T3W_STAGES - 1)
-        char* st = smem + (kt % T3W_STAGES) * T3W_STAGE_BYTES;
-        if (kt == nk - 1 && last_valid < T3_BK) {  // ragged end of the reduction: rows that do not exist must contribute 0
-            const int nbad = T3_BK - last_valid;
-            for (int idx = tid; idx < nbad * 80; idx += 512) {
-                const int r = last_valid + idx / 80, im = (idx % 80) >> 4, ch = idx & 15;
-                lds_write128(st, im * T3_IMG + r * 256 + ch * 16, make_uint4(0, 0, 0, 0));
-            }
-            __syncthreads();
-        }
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            const int row0 = 16 * ks + trow;
-            bf16x8 af[3], bf[NJ];
-#pragma unroll
-            for (int i = 0; i < 3; ++i) af[i] = join4(lds_tr_read(st, tr_off(offA[i], row0)), lds_tr_read(st, tr_off(offA[i], row0 + 4)));
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) bf[j] = join4(lds_tr_read(st, tr_off(offB[j], row0)), lds_tr_read(st, tr_off(offB[j], row0 + 4)));
-#pragma unroll
-            for (int i = 0; i < 3; ++i)
-#pragma unroll
-                for (int j = 0; j < NJ; ++j) acc[i][j] = mfma32(af[i], bf[j], acc[i][j]);
-        }
-        if (do_bias && (SWAP || (kt % tiles_q) == tq) && brg < BRG) {
-            const int im = (SWAP ? 3 : 0) + (bch >> 4), ci = bch & 15;
-            for (int r = brg; r < T3_BK; r += BRG) {
-                const int pcx = ((((ci >> 2) ^ (r & 3)) << 2) | (ci & 3));
-                const uint4 v = lds_read128(st, im * T3_IMG + r * 256 + pcx * 16);
-                bs[0] += __uint_as_float(v.x << 16); bs[1] += __uint_as_float(v.x & 0xffff0000u);
-                bs[2] += __uint_as_float(v.y << 16); bs[3] += __uint_as_float(v.y & 0xffff0000u);
-                bs[4] += __uint_as_float(v.z << 16); bs[5] += __uint_as_float(v.z & 0xffff0000u);
-                bs[6] += __uint_as_float(v.w << 16); bs[7] += __uint_as_float(v.w & 0xffff0000u);
-            }
-        }
-    }
-#undef T3W_ISSUE
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            const int q = q0 + wq * 32 * NJ + j * 32 + r32;
-            if constexpr (SWAP) {  // caller's layout: row q (its P index), column p (its Q index, a.P of them); registers 4g .. 4g + 3 = four consecutive p
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const int p = p0 + wp * 96 + i * 32 + 8 * g + 4 * h;
-                    const f32x4 v = {acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]};
-                    if (a.part) {
-                        *reinterpret_cast<f32x4*>(a.part + (size_t)split * a.part_stride + (size_t)q * a.P + p) = v;
-                    } else {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) atomicAdd(a.dW + (size_t)q * a.lddw + p + e, v[e]);
-                    }
-                }
-            } else {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int p = p0 + wp * 96 + i * 32 + acc_row(r, h);
-                    if (a.part) a.part[(size_t)split * a.part_stride + (size_t)p * a.Q + q] = acc[i][j][r];
-                    else atomicAdd(a.dW + (size_t)p * a.lddw + q, acc[i][j][r]);
-                }
-            }
-        }
-    if (a.dbias != nullptr) {  // (uniform over the workgroup)
-        __syncthreads();  // all stage reads are done: reuse the ring for the partial sums
-        float* red = reinterpret_cast<float*>(smem);
-        if (do_bias && brg < BRG) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) red[(brg * BCH + bch) * 8 + e] = bs[e];
-        }
-        __syncthreads();
-        if (do_bias && tid < BCH * 8) {
-            float sum = 0.f;
-#pragma unroll
-            for (int g = 0; g < BRG; ++g) sum += red[g * BCH * 8 + tid];
-            if constexpr (SWAP) {  // bias index = the caller's P index = this product's Q index: one row of Q floats per split
-                if (a.part) a.part[a.bias_off + (size_t)split * a.Q + q0 + tid] = sum;
-                else atomicAdd(a.dbias + q0 + tid, sum);
-            } else {
-                if (a.part) a.part[a.bias_off + ((size_t)split * tiles_q + tq) * a.P + p0 + tid] = sum;
-                else atomicAdd(a.dbias + p0 + tid, sum);
-            }
-        }
-    }
-}
-
-#endif  // DCV_TN_WIDE_Q
-
 __global__ __launch_bounds__(512) void gemm_tn384_kernel(GemmTnArgs a) {
     __shared__ __attribute__((aligned(16))) char smem[T3_STAGES * T3_STAGE_BYTES];  // 128 KB: one workgroup per CU
     tn384_body(a, xcd_remap(blockIdx.x, (a.Q / 128) * (a.P / 384) * a.splits), smem);
@@ -1890,21 +1496,11 @@ struct GemmTnGroup {
     GemmTnArgs d[TN_GROUP_MAX];
 };
 __global__ __launch_bounds__(512) void gemm_tn384_group_kernel(GemmTnGroup g) {
-#if DCV_TN_WIDE_Q
-    __shared__ __attribute__((aligned(16))) char smem[T3W_STAGES * T3W_STAGE_BYTES];  // 160 KB (the 384 x 128 products use 128 KB of it)
-    static_assert(T3W_STAGES * T3W_STAGE_BYTES >= T3_STAGES * T3_STAGE_BYTES, "ring sizes");
-#else
     __shared__ __attribute__((aligned(16))) char smem[T3_STAGES * T3_STAGE_BYTES];  // 128 KB: one workgroup per CU
-#endif
     const int id = xcd_remap(blockIdx.x, g.start[g.n]);
     int i = 0;
     while (i + 1 < g.n && id >= g.start[i + 1]) ++i;
     const GemmTnArgs a = g.d[i];
-#if DCV_TN_WIDE_Q
-    if constexpr ((DCV_TN_WIDE_Q & 1) != 0) { if (a.mode == 1) return tn384w_body<false>(a, id - g.start[i], smem); }
-    if constexpr ((DCV_TN_WIDE_Q & 2) != 0) { if (a.mode == 2) return tn384w_body<true>(a, id - g.start[i], smem); }
-    if constexpr ((DCV_TN_WIDE_Q & 4) != 0) { if (a.mode == 3) return tn384w_body<false, 3>(a, id - g.start[i], smem); }
-#endif
     tn384_body(a, id - g.start[i], smem);
 }
 
@@ -1951,7 +1547,7 @@ static int dcv_cu_count() {
 #ifndef DCV_WS_M_MIN
 #define DCV_WS_M_MIN 8192
 #endif
-// which kernel dcv_gemm_nt_ex launches for this problem (DCV_TILE_NARROW / _WIDE / _PAIR / _ALT / _WS), or a negative error for an illegal forced tile
+// which kernel dcv_gemm_nt_ex launches for this problem (DCV_TILE_NARROW / _WIDE / _PAIR / _WS), or a negative error for an illegal forced tile
 extern "C" int dcv_gemm_nt_pick(int M, int N, int K, int epilogue, int tile) {
     if (tile < DCV_TILE_AUTO || tile > DCV_TILE_AUTO_WS) return DCV_ERR_SHAPE;
     const bool legal384 = (N % N3_BN) == 0 && epilogue != DCV_EPI_PATCH;
@@ -1965,7 +1561,7 @@ extern "C" int dcv_gemm_nt_pick(int M, int N, int K, int epilogue, int tile) {
         tile = DCV_TILE_AUTO;
     }
     if (tile == DCV_TILE_WIDE) return legal384 ? DCV_TILE_WIDE : DCV_ERR_UNSUPPORTED;
-    if (tile == DCV_TILE_ALT) return (DCV_NT_ALT && legal384 && epilogue != DCV_EPI_BIAS_RESID_F32) ? DCV_TILE_ALT : DCV_ERR_UNSUPPORTED;
+    if (tile == DCV_TILE_ALT) return DCV_ERR_UNSUPPORTED;  // retired (docs/retired_experiments.md); the number stays reserved
     if (tile == DCV_TILE_NARROW) return DCV_TILE_NARROW;
     if (tile == DCV_TILE_PAIR) return epilogue != DCV_EPI_PATCH ? DCV_TILE_PAIR : DCV_ERR_UNSUPPORTED;
 #ifndef DCV_WIDE_K_MIN
@@ -2056,33 +1652,6 @@ extern "C" int dcv_gemm_nt_ex(const void* A, int lda, const void* W, int ldw, in
         DCV_LAUNCH_CHECK();
         return DCV_OK;
     }
-#if DCV_NT_ALT
-    if (pick == DCV_TILE_ALT) {
-        int ga = ((M + N3_BM - 1) / N3_BM) * (N / N3_BN);
-        if (ga > cap) ga = cap;
-        switch (epilogue) {
-            case DCV_EPI_BIAS_BF16:
-                if (!bias) return DCV_ERR_NULL;
-                hipLaunchKernelGGL(gemm_nt_alt_kernel<DCV_EPI_BIAS_BF16>, dim3(ga), dim3(512), 0, s, a);
-                break;
-            case DCV_EPI_BIAS_GELU_BF16:
-                if (!bias || !out2) return DCV_ERR_NULL;
-                hipLaunchKernelGGL(gemm_nt_alt_kernel<DCV_EPI_BIAS_GELU_BF16>, dim3(ga), dim3(512), 0, s, a);
-                break;
-            case DCV_EPI_PLAIN_BF16:
-                hipLaunchKernelGGL(gemm_nt_alt_kernel<DCV_EPI_PLAIN_BF16>, dim3(ga), dim3(512), 0, s, a);
-                break;
-            case DCV_EPI_GELU_BWD_BF16:
-                if (!aux) return DCV_ERR_NULL;
-                hipLaunchKernelGGL(gemm_nt_alt_kernel<DCV_EPI_GELU_BWD_BF16>, dim3(ga), dim3(512), 0, s, a);
-                break;
-            default:
-                return DCV_ERR_UNSUPPORTED;
-        }
-        DCV_LAUNCH_CHECK();
-        return DCV_OK;
-    }
-#endif
     if (pick == DCV_TILE_PAIR) {
         int gp = ((M + NP_BM - 1) / NP_BM) * ((N + NP_BN - 1) / NP_BN);
         if (gp > 2 * cap) gp = 2 * cap;  // two workgroups per CU
@@ -2181,7 +1750,7 @@ static int tn_launch(const void* Y, int ldy, const void* X, int ldx, int M, int 
         if (((uintptr_t)ws & 15) || (lddw % 4) || ((uintptr_t)dW & 15) || (dbias && ((uintptr_t)dbias & 15))) return DCV_ERR_ALIGN;
         if (ws_floats < need) return DCV_ERR_SHAPE;
     }
-    GemmTnArgs a{(const bf16_t*)Y, ldy, (const bf16_t*)X, ldx, M, P, Q, dW, lddw, dbias, mps, splits, ws, stride, bias_off, 0};
+    GemmTnArgs a{(const bf16_t*)Y, ldy, (const bf16_t*)X, ldx, M, P, Q, dW, lddw, dbias, mps, splits, ws, stride, bias_off};
     if (pick == DCV_TILE_WIDE) {
         hipLaunchKernelGGL(gemm_tn384_kernel, dim3((P / 384) * (Q / 128) * splits), dim3(512), 0, (hipStream_t)stream, a);
     } else {
@@ -2221,53 +1790,35 @@ extern "C" int dcv_gemm_tn_acc_det(const void* Y, int ldy, const void* X, int ld
 }
 
 // ---- grouped form (include/dcv.h: dcv_tn_item) --------------------------------------------------------------------------------------------
-// Per item: the tile form (0: 384 x 128; 1: 384 x 256; 2: 384 x 256 of the transposed product), its splits over the token rows and rows per split.  A
-// 384 x 256 tile is two units of work, so its products get twice the splits of the 384 x 128 ones: every workgroup of the launch does the same FLOPs.
+// The splits over the token rows and the rows per split are the same for every product, so every workgroup of the launch does the same FLOPs; per
+// item: its 384 x 128 tiles, the rows of its bias partials (one per split and column tile) and its offset in the workspace.
 struct TnGroupPlan {
-    int mode[TN_GROUP_MAX], splits[TN_GROUP_MAX], mps[TN_GROUP_MAX], tiles[TN_GROUP_MAX];
+    int splits, mps;
+    int tiles[TN_GROUP_MAX], bias_rows[TN_GROUP_MAX];
     long off[TN_GROUP_MAX];
     long need;
 };
 static int tn_group_plan(const dcv_tn_item* it, int n, int M, int cus, TnGroupPlan& pl) {
     if (!it) return DCV_ERR_NULL;
     if (n < 1 || n > TN_GROUP_MAX || M <= 0) return DCV_ERR_SHAPE;
-    int units = 0;  // in half tiles of 384 x 128
-    static const int weight[4] = {2, 4, 4, 3}, tile_q[4] = {128, 256, 0, 192};
+    int tiles = 0;
     for (int i = 0; i < n; ++i) {
         if (!it[i].Y || !it[i].X || !it[i].dW) return DCV_ERR_NULL;
         if (it[i].P <= 0 || it[i].Q <= 0 || (it[i].P % 384) || (it[i].Q % 128)) return DCV_ERR_UNSUPPORTED;
         if ((it[i].ldy % 8) || (it[i].ldx % 8) || ((uintptr_t)it[i].Y & 15) || ((uintptr_t)it[i].X & 15)) return DCV_ERR_ALIGN;
-        const int P = it[i].P, Q = it[i].Q;
-        if ((DCV_TN_WIDE_Q & 4) && (Q % 192) == 0) {
-            pl.mode[i] = 3;
-            pl.tiles[i] = (P / 384) * (Q / 192);
-        } else if ((DCV_TN_WIDE_Q & 1) && (Q % 256) == 0) {
-            pl.mode[i] = 1;
-            pl.tiles[i] = (P / 384) * (Q / 256);
-        } else if ((DCV_TN_WIDE_Q & 2) && (Q % 384) == 0 && (P % 256) == 0) {
-            pl.mode[i] = 2;
-            pl.tiles[i] = (Q / 384) * (P / 256);
-        } else {
-            pl.mode[i] = 0;
-            pl.tiles[i] = (P / 384) * (Q / 128);
-        }
-        units += pl.tiles[i] * weight[pl.mode[i]];
+        pl.tiles[i] = (it[i].P / 384) * (it[i].Q / 128);
+        tiles += pl.tiles[i];
     }
-    if (units > 2 * cus) return DCV_ERR_UNSUPPORTED;  // more than one resident round: call the products one by one
-    const int base2 = 2 * cus / units;  // splits of a 384 x 128 product
-    const int max3 = (M + T3_BK - 1) / T3_BK;
+    if (tiles > cus) return DCV_ERR_UNSUPPORTED;  // more than one resident round: call the products one by one
+    const int sp = std::min(cus / tiles, (M + T3_BK - 1) / T3_BK);
+    pl.mps = ((M + sp - 1) / sp + T3_BK - 1) / T3_BK * T3_BK;
+    pl.splits = (M + pl.mps - 1) / pl.mps;
     pl.need = 0;
     for (int i = 0; i < n; ++i) {
-        int sp = base2 * weight[pl.mode[i]] / 2;
-        if (sp < 1) sp = 1;
-        if (sp > max3) sp = max3;
-        const int mps = ((M + sp - 1) / sp + T3_BK - 1) / T3_BK * T3_BK;
-        pl.mps[i] = mps;
-        pl.splits[i] = (M + mps - 1) / mps;
-        // per item: [splits][P * Q] partial tiles (the caller's layout), then the bias partials: [splits * tiles_q][P], or [splits][P] for the transposed form
+        // per item: [splits][P * Q] partial tiles (the caller's layout), then the bias partials: [splits * tiles_q][P]
         pl.off[i] = pl.need;
-        const int bias_rows = pl.mode[i] == 2 ? pl.splits[i] : pl.splits[i] * (it[i].Q / tile_q[pl.mode[i]]);
-        pl.need += (long)pl.splits[i] * it[i].P * it[i].Q + (long)bias_rows * it[i].P;
+        pl.bias_rows[i] = pl.splits * (it[i].Q / 128);
+        pl.need += (long)pl.splits * it[i].P * it[i].Q + (long)pl.bias_rows[i] * it[i].P;
     }
     return DCV_OK;
 }
@@ -2285,25 +1836,19 @@ extern "C" int dcv_gemm_tn_group(const dcv_tn_item* items, int n, int M, float* 
     if (ws) {
         if ((uintptr_t)ws & 15) return DCV_ERR_ALIGN;
         if (ws_floats < pl.need) return DCV_ERR_SHAPE;
+        for (int i = 0; i < n; ++i)
+            if ((items[i].lddw % 4) || ((uintptr_t)items[i].dW & 15) || (items[i].dbias && ((uintptr_t)items[i].dbias & 15))) return DCV_ERR_ALIGN;
     }
-    for (int i = 0; i < n; ++i)
-        if ((items[i].lddw % 4) || ((uintptr_t)items[i].dW & 15) || (items[i].dbias && ((uintptr_t)items[i].dbias & 15))) {
-            if (ws || pl.mode[i] == 2) return DCV_ERR_ALIGN;
-        }
     GemmTnGroup g;
     g.n = n;
     int id = 0;
     for (int i = 0; i < n; ++i) {
         const dcv_tn_item& t = items[i];
         g.start[i] = id;
-        id += pl.tiles[i] * pl.splits[i];
+        id += pl.tiles[i] * pl.splits;
         const long stride = (long)t.P * t.Q;
-        if (pl.mode[i] == 2)  // the transposed product: operands exchanged; outputs keep the caller's layout
-            g.d[i] = GemmTnArgs{(const bf16_t*)t.X, t.ldx, (const bf16_t*)t.Y, t.ldy, M, t.Q, t.P, t.dW, t.lddw, t.dbias, pl.mps[i], pl.splits[i],
-                                ws ? ws + pl.off[i] : nullptr, stride, stride * pl.splits[i], 2};
-        else
-            g.d[i] = GemmTnArgs{(const bf16_t*)t.Y, t.ldy, (const bf16_t*)t.X, t.ldx, M, t.P, t.Q, t.dW, t.lddw, t.dbias, pl.mps[i], pl.splits[i],
-                                ws ? ws + pl.off[i] : nullptr, stride, stride * pl.splits[i], pl.mode[i]};
+        g.d[i] = GemmTnArgs{(const bf16_t*)t.Y, t.ldy, (const bf16_t*)t.X, t.ldx, M, t.P, t.Q, t.dW, t.lddw, t.dbias, pl.mps, pl.splits,
+                            ws ? ws + pl.off[i] : nullptr, stride, stride * pl.splits};
     }
     g.start[n] = id;
     for (int i = n + 1; i <= TN_GROUP_MAX; ++i) g.start[i] = id;
@@ -2317,9 +1862,8 @@ extern "C" int dcv_gemm_tn_group(const dcv_tn_item* items, int n, int M, float* 
             const dcv_tn_item& t = items[i];
             const long stride = (long)t.P * t.Q;
             float* w = ws + pl.off[i];
-            if (!det_jobs_add(jb, w, pl.splits[i], stride, t.dW, stride, t.Q, t.lddw)) return DCV_ERR_ALIGN;
-            const int bias_rows = pl.mode[i] == 2 ? pl.splits[i] : pl.splits[i] * (t.Q / (pl.mode[i] == 1 ? 256 : pl.mode[i] == 3 ? 192 : 128));
-            if (t.dbias && !det_jobs_add(jb, w + stride * pl.splits[i], bias_rows, t.P, t.dbias, t.P, t.P, t.P)) return DCV_ERR_ALIGN;
+            if (!det_jobs_add(jb, w, pl.splits, stride, t.dW, stride, t.Q, t.lddw)) return DCV_ERR_ALIGN;
+            if (t.dbias && !det_jobs_add(jb, w + stride * pl.splits, pl.bias_rows[i], t.P, t.dbias, t.P, t.P, t.P)) return DCV_ERR_ALIGN;
         }
         if (!det_reduce_multi(jb, (hipStream_t)stream)) return DCV_ERR_LAUNCH;
     }

@@ -52,7 +52,7 @@ int dcv_gemm_nt(const void* A, int lda, const void* W, int ldw, int M, int N, in
 #define DCV_TILE_NARROW 1
 #define DCV_TILE_WIDE 2
 #define DCV_TILE_PAIR 3 /* dcv_gemm_nt_ex only: 128 x 128 tiles by four-wave workgroups, TWO per CU (one stores while the other computes) */
-#define DCV_TILE_ALT 4  /* dcv_gemm_nt_ex only: 256 x 384 tiles whose two 192-column halves are accumulated and stored in alternating phases by the two wave groups of a workgroup (bf16-output epilogues, N % 384 == 0); compiled into variant builds only (-DDCV_NT_ALT=1: measured slower), DCV_ERR_UNSUPPORTED otherwise */
+#define DCV_TILE_ALT 4  /* RETIRED (docs/retired_experiments.md): the number stays reserved so that DCV_TILE_WS / DCV_TILE_AUTO_WS keep their values; dcv_gemm_nt_pick and dcv_gemm_nt_ex answer DCV_ERR_UNSUPPORTED */
 #define DCV_TILE_WS 5   /* dcv_gemm_nt_ex only: WEIGHT-STATIONARY kernel for K == 384, N % 384 == 0 and the bf16-output epilogues (BIAS_BF16,
                            BIAS_GELU_BF16, PLAIN_BF16, GELU_BWD_BF16): each workgroup holds one 384-column slice of W in registers and walks 32-row
                            panels of A; needs grid_cap (if set) >= N / 384, ldo2 / ldaux % 8 == 0 and 16-byte aligned out2 / aux / bias.  Outputs are

@@ -77,6 +77,7 @@ def test_gemm_tile_choice_rules():
     assert nt(M, 384, 256, hip.EPI_PATCH) == N_                # the tokeniser epilogue lives on the narrow kernel only
     assert nt(M, 200, 384, hip.EPI_PLAIN_BF16, W) < 0 and nt(M, 384, 256, hip.EPI_PATCH, W) < 0 and nt(M, 384, 384, 0, 7) < 0
     assert nt(M, 1152, 384, hip.EPI_BIAS_BF16, N_) == N_ and nt(M, 384, 384, hip.EPI_PLAIN_BF16, W) == W
+    assert nt(M, 1152, 384, hip.EPI_PLAIN_BF16, hip.TILE_ALT) < 0  # retired tile number (docs/retired_experiments.md): refused on a shape it once served
     # a few rounds of tiles: rounds x time per tile decides (256 CUs assumed when no device is present, as on the MI355X).
     # Measured on MI355X (tools/gemm_mid_m.py): M = 12 369 qkv 19.5 us narrow / 20.6 wide, fc1 37.7 / 32.1; M = 16 485 qkv 26.6 / 22.0,
     # fc1 43.8 / 52.3; M = 25 104 qkv 33.8 / 40.0, fc1T 45.3 / 48.0; M = 50 208 qkv 55.5 / 62.5, fc1T 69.7 / 53.1

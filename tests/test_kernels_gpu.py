@@ -126,21 +126,6 @@ def test_gemm_nt_384_wide_tiles(hip, M, N, K):
     _check_gemm_nt(hip, M, N, K, tile=hip.TILE_WIDE)
 
 
-def test_gemm_nt_alternating_halves(hip):
-    """gemm_nt_alt (TILE_ALT; variant builds only — ONE skip on the product library): the two wave groups of a workgroup accumulate and store the two 192-column
-    halves of a 256 x 384 tile in alternating phases on one shared LDS ring — every bf16-output epilogue, one to 24 k-stages per phase (fewer and more slots than the
-    six epilogue chunks), a partial last M tile, one tile per workgroup and long walks under a grid cap (an odd number of tiles per workgroup included), the headline
-    fc1 shape; the fp32 residual epilogue is refused."""
-    if hip.load().dcv_gemm_nt_pick(4100, 1152, 384, hip.EPI_PLAIN_BF16, hip.TILE_ALT) != hip.TILE_ALT:
-        pytest.skip("gemm_nt_alt is compiled into variant builds only (-DDCV_NT_ALT=1: measured slower than the shipped tiles, profiles/r05_x9_*)")
-    for M, N, K in [(4100, 1152, 384), (4352, 384, 1536), (4608, 1536, 384), (5000, 384, 64), (300, 384, 128), (9000, 768, 320), (64 * 1569, 1536, 384)]:
-        for grid_cap in (0, 3):
-            _check_gemm_nt(hip, M, N, K, resid=False, tile=hip.TILE_ALT, grid_cap=grid_cap)
-    A, W = _bf(256, 384, seed=1), _bf(384, 384, seed=2)
-    with pytest.raises(RuntimeError):
-        hip.gemm_nt(A, W, hip.EPI_BIAS_RESID_F32, torch.zeros(256, 384, device="cuda"), bias=_f(384, seed=3), tile=hip.TILE_ALT)
-
-
 # The headline step's GEMMs: M = 64 x 1569 = 100 416 token rows.  Both NT kernels are PERSISTENT: one workgroup per CU walks
 # 1 179 - 4 716 output tiles in several rounds, prefetching the next tile's first stages under the current tile's epilogue
 # (hand-counted vmcnt waits: csrc/gemm.hip `stores_behind`).  None of that runs when a launch has fewer tiles than CUs.
@@ -194,6 +179,8 @@ def test_gemm_nt_auto_tile_rules(hip):
     out = torch.empty(512, 200, dtype=torch.bfloat16, device="cuda")
     with pytest.raises(RuntimeError):
         hip.gemm_nt(A, W, hip.EPI_PLAIN_BF16, out, tile=hip.TILE_WIDE)  # N % 384 != 0
+    with pytest.raises(RuntimeError):
+        hip.gemm_nt(A, W, hip.EPI_PLAIN_BF16, out, tile=hip.TILE_ALT)  # retired tile number: refused before any launch
     hip.gemm_nt(A, W, hip.EPI_PLAIN_BF16, out, tile=hip.TILE_NARROW)
     _close(out, A.float() @ W.float().t(), 1e-2, 2e-2, "narrow")
 
