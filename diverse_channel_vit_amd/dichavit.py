@@ -346,6 +346,17 @@ class ChannelVisionTransformer(_Holder):
             nn.init.constant_(m.weight, 1.0)
 
 
+def layer_id_of(name: str, depth: int) -> int:
+    """Layer id of a DiChaViT parameter (by its named_parameters() name) for layer-wise learning-rate decay and freeze_prefix: 0 = the
+    tokeniser side (patch projection, cls_token, positional and channel embeddings, channel proxies), i + 1 = block i, depth + 1 = the
+    final norm, the head, `proxies` (and its alias `adaptive_interface.0`) and the learnable temperature."""
+    if name.startswith("feature_extractor.blocks."):
+        return int(name.split(".")[2]) + 1
+    if name.startswith("feature_extractor.") and not name.startswith("feature_extractor.norm."):
+        return 0
+    return depth + 1
+
+
 # ------------------------------------------------------------------------------------------------
 # the single autograd node: tokeniser + encoder on HIP kernels
 # ------------------------------------------------------------------------------------------------
@@ -353,14 +364,23 @@ class _EncoderFn(torch.autograd.Function):
     """inputs : x [B,Ct,H,W] f32, E [C,D] f32 (channel-embedding rows of this step), pos_tab [1+n,D] f32,
                 then the encoder parameters in arena order (model._enc_params).
        outputs: CLS feature after the final LayerNorm [B,D] f32, ortho statistics [B,2] f32.
+       FROZEN PREFIX (fine-tuning, DiChaViT.freeze_prefix): when nothing upstream of block k needs a gradient, blocks < k run as in an eval
+       forward (no activation kept, the stream updated in place; same output bits) and the backward stops above block k: no tokeniser
+       backward, dE and dpos are None.  k = depth is valid (only the final LayerNorm's backward runs).  Not with a DataParallel reducer.
        x gets a gradient when it requires one (dcv_patch_dgrad after the tokeniser's backward).  When only x does — no parameter, no E row,
        no positional table, no DataParallel reducer — the backward is DATA-ONLY: no weight-gradient GEMM, no gradient arena, no saved Xp."""
 
     @staticmethod
     def forward(ctx, model, ch_idx_dev, C, want_ortho, keep, tok, x, E, pos_tab, *params):
         need = ctx.needs_input_grad
+        # frozen prefix: nothing upstream of the first block k with a trainable parameter needs a gradient — not x, E, the positional table,
+        # cls_token or the patch projection (need[6:12]), and by k's definition no parameter of a block below it (12 per block from need[12])
+        frozen_k = None
+        if any(need[12:]) and not any(need[6:12]) and model._dp is None:
+            depth = len(model.feature_extractor.blocks)
+            frozen_k = next((bi for bi in range(depth) if any(need[12 + 12 * bi:24 + 12 * bi])), depth)
         st = model._run_forward(x, ch_idx_dev, C, E, pos_tab, want_ortho, save=any(need), keep=keep,
-                                st_scale=model._cur_scale, st_shift=model._cur_shift, tok=tok)
+                                st_scale=model._cur_scale, st_shift=model._cur_shift, tok=tok, **({} if frozen_k is None else dict(frozen_k=frozen_k)))
         if need[6]:  # dcv_patch_dgrad's operands: the bf16 projection copy this forward multiplied by, the channel index, the input affine's scale
             fe = model.feature_extractor
             P = fe.patch_size
@@ -596,8 +616,9 @@ class DiChaViT(nn.Module):
         and allocate 86 MB)."""
         ga = self._grad_arena
         if ga is not None:
-            busy = any(p.grad is not None and p.grad.untyped_storage().data_ptr() == ga.untyped_storage().data_ptr()
-                       for p in (self._enc_params[0], self._enc_params[2], self._enc_params[-1]))
+            first = next((p for p in self._enc_params if p.grad is not None), None)  # cls_token unless a prefix is frozen
+            busy = any(p is not None and p.grad is not None and p.grad.untyped_storage().data_ptr() == ga.untyped_storage().data_ptr()
+                       for p in (first, self._enc_params[2], self._enc_params[-1]))
             if not busy:
                 ga.zero_()
                 return ga
@@ -609,6 +630,31 @@ class DiChaViT(nn.Module):
         ga = torch.zeros(self._enc_size, dtype=torch.float32, device=self._arena.device)
         self._grad_arena = ga
         return ga
+
+    # ---------------------------------------------------------------------------------------
+    # fine-tuning
+    # ---------------------------------------------------------------------------------------
+    def freeze_prefix(self, n_blocks: int, tokeniser: bool = True):
+        """Fine-tuning with a frozen prefix: requires_grad_(False) on the tokeniser-side parameters (layer id 0 of `layer_id_of`: patch
+        projection, cls_token, positional and channel embeddings, channel proxies) when `tokeniser`, and on blocks < n_blocks; every other
+        tokeniser-side / block parameter is set trainable again, so freeze_prefix(0, tokeniser=False) undoes it (a channel embedding frozen
+        by cfg.freeze_channel_emb stays frozen).  The final norm, the head and `proxies` are not touched.  With the tokeniser and the
+        first k blocks frozen the forward keeps no activation of those blocks and the backward stops above block k (_EncoderFn).  Returns
+        the model."""
+        depth = len(self.feature_extractor.blocks)
+        if not 0 <= int(n_blocks) <= depth:
+            raise ValueError(f"n_blocks must be in [0, {depth}]")
+        keep_frozen = set()
+        pe = self.feature_extractor.patch_embed
+        if _cfg_get(self.cfg, "freeze_channel_emb", False) and hasattr(pe, "channel_embed"):
+            keep_frozen.add(id(pe.channel_embed.weight))
+        for name, p in self.named_parameters():
+            lid = layer_id_of(name, depth)
+            if lid == 0:
+                p.requires_grad_(not tokeniser and id(p) not in keep_frozen)
+            elif lid <= depth:
+                p.requires_grad_(lid - 1 >= n_blocks)
+        return self
 
     # ---------------------------------------------------------------------------------------
     # host-side pieces of PatchEmbedPerChannel.forward (dichavit.py:110-417)
@@ -827,8 +873,11 @@ class DiChaViT(nn.Module):
         return out
 
     def _run_forward(self, x, ch_idx_dev, C, E, pos_tab, want_ortho, save, keep=None, st_scale=None, st_shift=None, tok=None, probe=None,
-                     capture=None):
-        """probe=(layer, rows): get_last_selfattention — run blocks < layer as the forward does, stop at block `layer` after its norm1 and qkv
+                     capture=None, frozen_k=None):
+        """frozen_k=k (with save): blocks < k and the tokeniser keep nothing for the backward (they run as with save=False, on the same
+        kernels); st["layers"] still has one entry per block — the backward indexes it by block number — which for blocks < k holds the
+        DropPath factors only.
+        probe=(layer, rows): get_last_selfattention — run blocks < layer as the forward does, stop at block `layer` after its norm1 and qkv
         GEMM and return its attention probabilities [B, H, rows, N] (fp32) instead of the state.  Needs save=False and want_ortho=False.  The
         model's operand copies (_bf16, _bf16_t, _qbias) and _sr_seed are left alone — a training forward's backward may still read them — and
         round-to-nearest straight copies are cast into scratch instead.
@@ -860,7 +909,8 @@ class DiChaViT(nn.Module):
         # (channels, positions) structure of the embedding rows the tokeniser epilogue adds: (C, n) normally, (1, C*n) when the
         # positional table is per token (the reference's early-out, _pos_table)
         Ctok, ntok = tok if tok is not None else (C, n)
-        st = dict(B=B, C=C, n=n, N=N, M=M, save=save, tok=(Ctok, ntok), ps=ps)
+        fk = frozen_k if save else None
+        st = dict(B=B, C=C, n=n, N=N, M=M, save=save, tok=(Ctok, ntok), ps=ps, frozen_k=fk)
         # --- tokeniser: im2col -> MFMA GEMM with (+bias +channel_embed[c] +pos[i]) epilogue ---
         Xp = torch.empty(B * T, P * P, dtype=bf, device=dev)
         hip.im2col(x, ch_idx_dev, Xp, B, Ct, C, Hi, Wi, P, scale=st_scale, shift=st_shift)
@@ -877,9 +927,9 @@ class DiChaViT(nn.Module):
             tot = torch.empty(B, D, dtype=f32, device=dev)
             inv = torch.empty(B, T, dtype=f32, device=dev)
             hip.ortho_fwd(Y, S, selfsq, tot, inv, stats, B, C, n, D)
-            if save:
+            if save and fk is None:
                 st.update(Y=Y, S=S, tot=tot, inv=inv)
-        if save:
+        if save and fk is None:
             st["Xp"] = Xp
         if keep is not None:  # dropout_tokens_hcs: the encoder sees only the kept token rows (CLS first)
             keep_dev = self._index_tensor(keep, torch.int32, dev, cache=False)
@@ -904,6 +954,7 @@ class DiChaViT(nn.Module):
         pre_ln = None
         for bi, blk in enumerate(fe.blocks):
             L = {}
+            sv = save and (fk is None or bi >= fk)  # this block's activations are kept for the backward
             tail = self.cls_only_tail and bi == len(fe.blocks) - 1 and capture is None  # a captured last block runs on all rows
             dsc = drop[bi] if drop is not None else None  # (attention branch, MLP branch) factors [B] or None
             if pre_ln is not None:  # norm1 of this block came out of the previous block's fc2 + residual epilogue
@@ -939,7 +990,7 @@ class DiChaViT(nn.Module):
             else:
                 hip.attn_fwd(qkv, o, lse, B, N, H, D // H, scale, prescaled=ps)
                 o_c = None
-                xmid = torch.empty(M, D, dtype=f32, device=dev) if save else xcur
+                xmid = torch.empty(M, D, dtype=f32, device=dev) if sv else xcur
                 R = M
                 if fuse_ln:
                     # attn.proj + residual AND norm2 from the accumulators of one launch (dcv_gemm_nt_resid_ln): no re-read of xmid
@@ -957,7 +1008,7 @@ class DiChaViT(nn.Module):
             z = torch.empty(R, 4 * D, dtype=bf, device=dev)  # GELU'(pre-activation), saved for the backward
             hact = torch.empty(R, 4 * D, dtype=bf, device=dev)
             hip.gemm_nt(u2, wb(blk.mlp.fc1.weight), hip.EPI_BIAS_GELU_BF16, z, bias=blk.mlp.fc1.bias, out2=hact)
-            xout = torch.empty(R, D, dtype=f32, device=dev) if (save or tail) else xmid
+            xout = torch.empty(R, D, dtype=f32, device=dev) if (sv or tail) else xmid
             # a capture that ends at this block keeps this launch although block bi + 1 never runs: the stream of block bi must come from the
             # same kernel whether or not later blocks are requested (n=4 equals four single-index calls bit for bit), at the cost of one unused
             # norm1 output in the epilogue
@@ -972,7 +1023,9 @@ class DiChaViT(nn.Module):
             else:
                 hip.gemm_nt(hact, wb(blk.mlp.fc2.weight), hip.EPI_BIAS_RESID_F32, xout, bias=blk.mlp.fc2.bias, aux=xmid,
                             **(dict(aux2=dsc[1], T=R // B) if dsc else {}))
-            if save:
+            if save and not sv:
+                layers.append(dict(drop=dsc))  # a frozen block: only what the block above reads from it
+            if sv:
                 L.update(drop=dsc)
                 L.update(x_in=xcur, u1=u1, mean1=mean1, rstd1=rstd1, qkv=qkv, o=o, lse=lse, x_mid=xmid, u2=u2, mean2=mean2,
                          rstd2=rstd2, z=z, h=hact, tail=tail, o_c=o_c)
@@ -1068,11 +1121,14 @@ class DiChaViT(nn.Module):
             dp.grad_ready(ga, *self._range_of([fe.norm.weight, fe.norm.bias]))
         scale = 64 ** -0.5
         ps = bool(st.get("ps"))  # the forward of this pass ran with pre-scaled q: qkv holds q', the backward entries must match
-        dz = torch.empty(M, 4 * D, dtype=bf, device=dev)
-        du = torch.empty(M, D, dtype=bf, device=dev)
-        dO = torch.empty(M, D, dtype=bf, device=dev)
-        dqkv = torch.empty(M, 3 * D, dtype=bf, device=dev)
-        delta = torch.empty(2, B, H, N, dtype=f32, device=dev)  # attention backward workspace: -delta, lse*log2e
+        fk = st.get("frozen_k")  # frozen prefix: the loop stops above block fk and the tokeniser's backward is not launched
+        k0 = 0 if fk is None else fk
+        Ms = M if k0 < len(fe.blocks) else 0  # fk == depth: only the final LayerNorm's backward (above) runs
+        dz = torch.empty(Ms, 4 * D, dtype=bf, device=dev)
+        du = torch.empty(Ms, D, dtype=bf, device=dev)
+        dO = torch.empty(Ms, D, dtype=bf, device=dev)
+        dqkv = torch.empty(Ms, 3 * D, dtype=bf, device=dev)
+        delta = torch.empty(2, B, H, N if Ms else 0, dtype=f32, device=dev)  # attention backward workspace: -delta, lse*log2e
         # Weight-gradient products on a second stream (self.wgrad_stream): nothing in the backward depends on them, so their
         # workgroups fill the tail of the input-gradient / attention kernels and their atomic flush overlaps the next kernel.
         # Hazards are the scratch buffers they read (dxb, dz, dqkv: the main stream waits for the last side-stream reader
@@ -1139,7 +1195,7 @@ class DiChaViT(nn.Module):
         # a reader before it overwrites one.  Those waits were always satisfied long before, but each is a barrier packet in the compute
         # queue (4 per layer) and cost ~8 us of queue time: 36.58 -> 36.23 ms per step, same bits (profiles/r03_x12_*).
         private = bool(self.wgrad_private_scratch)  # on one stream too: the grouped weight-gradient launch below needs its operands alive
-        for li in range(len(fe.blocks) - 1, -1, -1):
+        for li in range(len(fe.blocks) - 1, k0 - 1, -1):
             blk, L = fe.blocks[li], st["layers"][li]
             tail = L["tail"]
             side = None if tail else side_all
@@ -1204,6 +1260,10 @@ class DiChaViT(nn.Module):
                     dxb, dxb_alt = dxb_alt, dxb
                 before_write(id(dxb))
             below = st["layers"][li - 1].get("drop") if li > 0 else None  # the copy written here feeds the MLP branch of the block below
+            # At the first trainable block above a frozen prefix (li == k0 > 0) nobody reads what this launch writes for the block below (dx,
+            # and dxb with that block's DropPath factors): the loop ends here.  The launch stays as it is, for norm1's own weight and bias
+            # gradients come out of the same kernel, which reads the full-size dx as the residual gradient (the CLS-only tail's zero-filled
+            # one included); the two unread stores are 0.23 of the launch's 0.62 GB at the headline shape, once per backward, and the kernel has no form without them.
             hip.ln_bwd(du, L["x_in"], L["mean1"], L["rstd1"], blk.norm1.weight, dx, dx, dxb, g(blk.norm1.weight), g(blk.norm1.bias), M, D,
                        **(dict(bf16_row_scale=below[1], rows_per_sample=N) if below else {}))
             if side is not None:
@@ -1236,6 +1296,8 @@ class DiChaViT(nn.Module):
                     dp.grad_ready(ga, *self._range_of([blk.norm1.weight, blk.mlp.fc2.bias]))
         join()
         held.clear()
+        if fk is not None:
+            return None, None, [self._gview(ga, p) if p.requires_grad else None for p in self._enc_params]
         # --- tokeniser ---
         if st.get("keep_dev") is not None:  # adjoint of the token gather: dropped tokens receive no gradient
             Nf = st["N_full"]

@@ -70,6 +70,8 @@ _SIGS = {
     "dcv_adamw": ([_vp, _vp, _vp, _vp, _l, _f, _f, _f, _f, _f, _i, _f, _vp], _i),
     "dcv_adamw_dyn": ([_vp, _vp, _vp, _vp, _l, _vp, _vp], _i),
     "dcv_adamw_set_hyper": ([_vp, _f, _f, _f, _f, _f, _i, _f, _vp], _i),
+    "dcv_adamw_set_hyper_groups": ([_vp, _vp, _vp, _i, _f, _vp], _i),
+    "dcv_adamw_groups": ([_vp, _vp, _vp, _vp, _l, _vp, _vp, _i, _vp, _i, _vp], _i),
     "dcv_cast_bf16": ([_vp, _vp, _l, _vp], _i),
     "dcv_cast_transpose_bf16": ([_vp, _vp, _vp, _i, _i, _vp], _i),
     "dcv_sumsq_acc": ([_vp, _l, _vp, _vp], _i),
@@ -496,6 +498,23 @@ def adamw_dyn(p, g, m, v, n, hyper_dev):
 
 def adamw_set_hyper(hyper_dev, lr, b1, b2, eps, wd, step, grad_scale=1.0):
     _check(load().dcv_adamw_set_hyper(_p(hyper_dev), lr, b1, b2, eps, wd, step, grad_scale, _stream()), "dcv_adamw_set_hyper")
+
+
+ADAMW_MAX_GROUPS, ADAMW_MAX_SEGS = 32, 1024  # include/dcv.h DCV_ADAMW_MAX_GROUPS / DCV_ADAMW_MAX_SEGS
+
+
+def adamw_set_hyper_groups(hyper_dev, rows, steps, grad_scale=1.0):
+    """rows: per group (lr, b1, b2, eps, wd); steps: per group step count (>= 1).  Host lists: they travel by value."""
+    n = len(rows)
+    r = (C.c_float * (5 * n))(*[float(x) for row in rows for x in row])
+    s = (C.c_int * n)(*[int(x) for x in steps])
+    _check(load().dcv_adamw_set_hyper_groups(_p(hyper_dev), C.cast(r, C.c_void_p), C.cast(s, C.c_void_p), n, grad_scale, _stream()),
+           "dcv_adamw_set_hyper_groups")
+
+
+def adamw_groups(p, g, m, v, n, seg_end4, seg_group, n_seg, hyper_dev, n_groups):
+    _check(load().dcv_adamw_groups(_p(p), _p(g), _p(m), _p(v), n, _p(seg_end4), _p(seg_group), n_seg, _p(hyper_dev), n_groups, _stream()),
+           "dcv_adamw_groups")
 
 
 def cast_bf16(src, dst, n):

@@ -253,6 +253,21 @@ int dcv_adamw_dyn(float* p, const float* g, float* m, float* v, long n, const fl
  * scalars of a step that has not executed yet. */
 int dcv_adamw_set_hyper(float* hyper_dev, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
                         float grad_scale, void* stream);
+/* AdamW with PARAMETER GROUPS over the flat arena (csrc/optim_groups.hip): one launch whatever the number of groups, frozen
+ * parameters included — the DINO decay / no-decay split, layer-wise learning-rate decay, fine-tuning with a frozen prefix. */
+#define DCV_ADAMW_MAX_GROUPS 32    /* 32 x 8 floats = 1 KB, passed by value; LLRD at depth 12 with a decay / no-decay split needs 2 x 14 = 28 */
+#define DCV_ADAMW_MAX_SEGS   1024  /* DiChaViT has 149 encoder tensors; 8 KB of LDS for the table */
+/* hyper_dev[n_groups][8], one row per group in dcv_adamw_set_hyper's layout {lr, b1, b2, eps, wd, 1/bc1, 1/sqrt(bc2), grad_scale};
+ * rows_host[n_groups][5] = {lr, b1, b2, eps, wd}, steps_host[n_groups] >= 1 (bias corrections in double on the host, as
+ * dcv_adamw_set_hyper).  The rows travel BY VALUE as the argument of one small kernel: stream-ordered, no staging buffer. */
+int dcv_adamw_set_hyper_groups(float* hyper_dev, const float* rows_host, const int* steps_host, int n_groups, float grad_scale, void* stream);
+/* One launch over p, g, m, v [n] (n % 4 == 0, 16-byte aligned).  seg_end4 / seg_group: device int32 [n_seg], sorted runs that cover
+ * [0, n / 4) in float4 units: run s is [seg_end4[s-1], seg_end4[s]) and takes hyper row seg_group[s]; seg_group[s] == -1 is a
+ * SKIPPED run: p, m, v are not written and g is not read there (a row index outside [0, n_groups) skips too; float4 past the last
+ * end belong to the last run; nothing outside [0, n) is touched whatever the table holds).  Element update = dcv_adamw_dyn's with
+ * that row, bit for bit. */
+int dcv_adamw_groups(float* p, const float* g, float* m, float* v, long n, const int* seg_end4, const int* seg_group, int n_seg,
+                     const float* hyper_dev, int n_groups, void* stream);
 /* Gradient clipping (trainer.py:1003-1004 -> torch.nn.utils.clip_grad_norm_, L2): dcv_sumsq_acc adds sum(x^2) of a flat fp32
  * range to the device scalar *acc (zero it first; call once per gradient buffer); dcv_clip_scale multiplies a range by
  * min(1, max_norm / (sqrt(*sumsq_dev) + 1e-6)).  Everything stays on the device: no host sync, graph-capturable. */
