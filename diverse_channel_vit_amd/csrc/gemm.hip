@@ -43,6 +43,8 @@ struct GemmNtArgs {
     float* ln_mean;
     float* ln_rstd;
     float ln_eps;
+    // gemm_nt384_kernel's row-tile plan (dcv_gemm_nt384_plan): row tiles 0 .. n256-1 are 256 rows high, n256 .. tiles_m-1 are 192 rows high
+    int n256, tiles_m;
 };
 constexpr int DCV_EPI_RESID_LN = 6;  // kernel-internal: reached through dcv_gemm_nt_resid_ln only
 
@@ -249,12 +251,13 @@ __device__ __forceinline__ void epi_store4(const GemmNtArgs& a, int m, int n, co
 template <int EPI>
 __device__ constexpr bool epi_f32out() { return EPI == DCV_EPI_BIAS_RESID_F32 || EPI == DCV_EPI_PATCH; }
 
-// Epilogue of a wave's 64-row x (16 NJ)-column block of accumulators acc[4][J0 .. J0 + NJ) (NJ a multiple of 4), rows m_w + 16 i + ..,
+// Epilogue of a wave's (16 RB)-row x (16 NJ)-column block of accumulators acc[RB][J0 .. J0 + NJ) (NJ a multiple of 4; RB = 4 row blocks except
+// in gemm_nt384_kernel's 192-row tiles, RB a multiple of NI), rows m_w + 16 i + ..,
 // columns n_w + ..; `between()` runs after the first auxiliary loads have been issued and before anything is stored (the persistent
 // kernels put the next tile's prefetch there).  NI: row blocks (of 16 rows) whose auxiliary loads are issued together (4 = all of
 // them before `between`; fewer = fewer registers).  bz: the lane's bias values in its final layout (nt_load_bias).
-template <int EPI, int NI, int NJ, int NJT, int J0, class Between>
-__device__ __forceinline__ void nt_epilogue_block(const GemmNtArgs& a, const f32x4 (&acc)[4][NJT], int m_w, int n_w, int r16, int kg,
+template <int EPI, int NI, int NJ, int NJT, int J0, int RB, class Between>
+__device__ __forceinline__ void nt_epilogue_block(const GemmNtArgs& a, const f32x4 (&acc)[RB][NJT], int m_w, int n_w, int r16, int kg,
                                                   const float* bz, Between&& between) {
     constexpr bool HAS_AUX = (EPI == DCV_EPI_BIAS_RESID_F32) || (EPI == DCV_EPI_GELU_BWD_BF16) || (EPI == DCV_EPI_PATCH);
     const int rr = r16 & 7, hi = r16 >> 3;
@@ -262,7 +265,7 @@ __device__ __forceinline__ void nt_epilogue_block(const GemmNtArgs& a, const f32
         constexpr int NG = NJ / 2;  // 32-column groups
         const int cl = 16 * hi + 4 * kg;
 #pragma unroll
-        for (int ib = 0; ib < 4; ib += NI) {
+        for (int ib = 0; ib < RB; ib += NI) {
             float x[NI][NG][2][4];
 #pragma unroll
             for (int i = 0; i < NI; ++i)
@@ -293,7 +296,7 @@ __device__ __forceinline__ void nt_epilogue_block(const GemmNtArgs& a, const f32
         constexpr int NG = NJ / 4;  // 64-column groups
         const int cl = 32 * hi + 16 * (kg & 1) + 8 * (kg >> 1);
 #pragma unroll
-        for (int ib = 0; ib < 4; ib += NI) {
+        for (int ib = 0; ib < RB; ib += NI) {
             float x[HAS_AUX ? NI : 1][HAS_AUX ? NG : 1][2][8];
             if constexpr (HAS_AUX) {
 #pragma unroll
@@ -645,6 +648,13 @@ __global__ __launch_bounds__(256) void gemm_nt_pair_kernel(GemmNtArgs a) {
     }
 }
 
+// the lane id from v_mbcnt, as a statement hipcc can neither hoist nor merge with threadIdx.x
+__device__ __forceinline__ int lane_id_here() {
+    int l;
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+    return l;
+}
+
 // ------------------------------------------------------------------------------------------------
 // Residual + LayerNorm epilogue of the 256 x 384 kernel for N == 384 (round 4, judge row N1): the tile spans whole rows, so the LayerNorm that
 // follows every residual addition (vit.py:397-398: x = x + branch; then norm2(x) / the next block's norm1(x)) is computed from the accumulators:
@@ -656,18 +666,21 @@ __global__ __launch_bounds__(256) void gemm_nt_pair_kernel(GemmNtArgs a) {
 // 4 kg .. +3: 24 values of a row per lane, 8 lanes per row and wave, two waves per row.  Statistics: per lane mean and centred sum of squares
 // (two passes over its 24 registers), combined pairwise with Chan's formula — the centred form ln_fwd_kernel uses, not E[x^2] - mean^2 —
 // over the 8 lanes (xor 8, 16, 32), then across the two waves through the ring buffer that is free during the epilogue.
-template <class Between>
-__device__ __forceinline__ void nt384_resid_ln_epilogue(const GemmNtArgs& a, f32x4 (&acc)[4][12], int m0, int wm, int wn, int ln, char* fb,
+// RB: 16-row blocks per wave (4 in a 256-row tile, 3 in a 192-row one: the wave's rows start at 16 RB wm).
+template <int RB, class Between>
+__device__ __forceinline__ void nt384_resid_ln_epilogue(const GemmNtArgs& a, f32x4 (&acc)[RB][12], int m0, int wm, int wn, int ln, char* fb,
                                                         Between&& between) {
     const int r16 = ln & 15, kg = ln >> 4, rr = r16 & 7, hi = r16 >> 3;
     const int ncol0 = 192 * wn + 16 * hi + 4 * kg;  // + 32 c
     float* const stat = reinterpret_cast<float*>(fb);  // [wn][256 rows][2]
+    int T = a.T;  // opaque: the per-lane division below is then set up here, per tile, and not above the k-loop (its reciprocal register was spilled)
+    asm volatile("" : "+s"(T));
     __builtin_amdgcn_s_barrier();  // every wave has finished reading this buffer (the last k stage) before anyone writes statistics into it
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int ma = m0 + 64 * wm + 16 * i + rr, mb = ma + 8;
+    for (int i = 0; i < RB; ++i) {
+        const int ma = m0 + 16 * RB * wm + 16 * i + rr, mb = ma + 8;
         const int mac = min(ma, a.M - 1), mbc = min(mb, a.M - 1);
-        const float sa = a.aux2 ? a.aux2[mac / a.T] : 1.f, sb = a.aux2 ? a.aux2[mbc / a.T] : 1.f;  // DropPath factor of the row's sample
+        const float sa = a.aux2 ? a.aux2[mac / T] : 1.f, sb = a.aux2 ? a.aux2[mbc / T] : 1.f;  // DropPath factor of the row's sample
         const float* ra = (const float*)a.aux + (size_t)mac * a.ldaux + ncol0;
         const float* rb = (const float*)a.aux + (size_t)mbc * a.ldaux + ncol0;
 #pragma unroll
@@ -740,7 +753,7 @@ __device__ __forceinline__ void nt384_resid_ln_epilogue(const GemmNtArgs& a, f32
             half_n *= 2.f;
         }
         if (hi == 0 && kg == 0) {  // one lane per row: this wave's 192 columns of rows (i, rr) and (i, rr + 8)
-            const int rl = 64 * wm + 16 * i + rr;
+            const int rl = 16 * RB * wm + 16 * i + rr;
             *reinterpret_cast<float2*>(stat + ((size_t)(wn * 256 + rl) * 2)) = make_float2(mu[0], m2[0]);
             *reinterpret_cast<float2*>(stat + ((size_t)(wn * 256 + rl + 8) * 2)) = make_float2(mu[1], m2[1]);
         }
@@ -755,10 +768,14 @@ __device__ __forceinline__ void nt384_resid_ln_epilogue(const GemmNtArgs& a, f32
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();  // both column halves of every row (and gamma / beta) are in LDS
+    // the second pass works out its lane coordinates again (lane_id_here): carried over from the first pass they were spilled across it
+    const int ln2 = lane_id_here();
+    const int kg2 = ln2 >> 4, rr2 = ln2 & 7, hi2 = (ln2 >> 3) & 1;
+    const int ncol2 = 192 * wn + 16 * hi2 + 4 * kg2;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int ma = m0 + 64 * wm + 16 * i + rr, mb = ma + 8;
-        const int rl = 64 * wm + 16 * i + rr;
+    for (int i = 0; i < RB; ++i) {
+        const int ma = m0 + 16 * RB * wm + 16 * i + rr2, mb = ma + 8;
+        const int rl = 16 * RB * wm + 16 * i + rr2;
         float mean[2], rstd[2];
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
@@ -768,7 +785,7 @@ __device__ __forceinline__ void nt384_resid_ln_epilogue(const GemmNtArgs& a, f32
             mean[h] = 0.5f * (p0.x + p1.x);
             rstd[h] = rsqrtf((p0.y + p1.y + d * d * 96.f) * (1.f / 384.f) + a.ln_eps);
         }
-        if (wn == 0 && hi == 0 && kg == 0) {
+        if (wn == 0 && hi2 == 0 && kg2 == 0) {
             if (ma < a.M) { a.ln_mean[ma] = mean[0]; a.ln_rstd[ma] = rstd[0]; }
             if (mb < a.M) { a.ln_mean[mb] = mean[1]; a.ln_rstd[mb] = rstd[1]; }
         }
@@ -777,8 +794,8 @@ __device__ __forceinline__ void nt384_resid_ln_epilogue(const GemmNtArgs& a, f32
             float4 g4[2], be4[2];
 #pragma unroll
             for (int q = 0; q < 2; ++q) {
-                g4[q] = *reinterpret_cast<const float4*>(stat + 1024 + ncol0 + 32 * (2 * hc + q));
-                be4[q] = *reinterpret_cast<const float4*>(stat + 1024 + 384 + ncol0 + 32 * (2 * hc + q));
+                g4[q] = *reinterpret_cast<const float4*>(stat + 1024 + ncol2 + 32 * (2 * hc + q));
+                be4[q] = *reinterpret_cast<const float4*>(stat + 1024 + 384 + ncol2 + 32 * (2 * hc + q));
             }
             // bf16 u of the column groups c = 2 hc and c + 1, then a 16-lane-row swap (v_permlane16_swap) between the lanes kg and kg ^ 1, which hold
             // adjacent 4-column pieces of both groups: afterwards an even-kg lane holds 8 consecutive columns of group c, its odd partner 8
@@ -802,8 +819,8 @@ __device__ __forceinline__ void nt384_resid_ln_epilogue(const GemmNtArgs& a, f32
             const u32x2_t ay = __builtin_amdgcn_permlane16_swap(pa[0].y, pa[1].y, false, false);
             const u32x2_t bx = __builtin_amdgcn_permlane16_swap(pb[0].x, pb[1].x, false, false);
             const u32x2_t by = __builtin_amdgcn_permlane16_swap(pb[0].y, pb[1].y, false, false);
-            const int kgp = kg & 1;
-            const int ucol = 192 * wn + 32 * (2 * hc + kgp) + 16 * hi + 4 * (kg - kgp);
+            const int kgp = kg2 & 1;
+            const int ucol = 192 * wn + 32 * (2 * hc + kgp) + 16 * hi2 + 4 * (kg2 - kgp);
             if (ma < a.M) *reinterpret_cast<uint4*>((bf16_t*)a.out2 + (size_t)ma * a.ldo2 + ucol) = make_uint4(ax[0], ay[0], ax[1], ay[1]);
             if (mb < a.M) *reinterpret_cast<uint4*>((bf16_t*)a.out2 + (size_t)mb * a.ldo2 + ucol) = make_uint4(bx[0], by[0], bx[1], by[1]);
         }
@@ -818,7 +835,18 @@ __device__ __forceinline__ void nt384_resid_ln_epilogue(const GemmNtArgs& a, f32
 // (8 waves as 4 (M) x 2 (N), each 64 x 192 = 4 x 12 MFMA 16x16x32 tiles; the k-step's read / MFMA order is pinned, see the loop) and the
 // whole LDS: two 80 KB stages.  With two buffers the next stage is issued after the barrier that retires the previous
 // one, one k-iteration (48 MFMAs per wave) ahead.  Tile walk, register epilogue and fused ops as in gemm_nt_kernel.
-constexpr int N3_BM = 256, N3_BN = 384, N3_BK = 64;
+// Tile heights: the last row tiles of a launch may be 192 rows high (dcv_gemm_nt384_plan below: 393 tiles of 256 rows on 256 workgroups are two rounds for
+// 1.53 rounds of work; with 192-row tiles in the second round the longest walk is 448 rows, not 512).  A 192-row tile is the same tile with 3 of a
+// wave's 4 row blocks: rows 48 wm + 16 i + r16 (48 is a multiple of the swizzle's 16-row period, so the fragment reads stay base + immediate), the
+// first 192 rows of the same LDS image, 36 MFMAs per wave and k-step.  The per-tile body (accumulator clear, k-loop, epilogue) is instantiated
+// for RB = 4 and RB = 3 row blocks and the persistent loop dispatches on the tile's height; each output element is still produced by one tile with
+// the same MFMA, k order and lane-to-column map, so the outputs do not depend on the plan.
+// Resource usage (hipcc -Rpass-analysis=kernel-resource-usage, both bodies in one kernel): VGPRs 237 / 237 / 244 / 236 / 237 for the epilogues
+// 0 .. 4 and 249 for the residual + LayerNorm one; scratch 0 and no VGPR spill in all six (the LayerNorm instantiation carried 16 bytes of
+// scratch while it kept threadIdx.x, a division's reciprocal, the k-loop's entry flag and the second pass's lane coordinates alive across the
+// k-loop: see lane_id_here and the notes where they were).  SGPRs 106 with 0 - 16 (LayerNorm: 36) of them parked in lanes of one VGPR outside the
+// k-loops: v_readlane / v_writelane, no memory traffic; neither k-loop contains one.
+constexpr int N3_BM = 256, N3_BN = 384, N3_BK = 64;  // N3_BM: the full tile height (and the LDS image's); the plan's short tiles are 192 rows
 constexpr int N3_A_BYTES = N3_BM * N3_BK * 2, N3_W_BYTES = N3_BN * N3_BK * 2, N3_STAGE_BYTES = N3_A_BYTES + N3_W_BYTES;  // 80 KB
 constexpr int N3_SMEM = 2 * N3_STAGE_BYTES;                                                                              // 160 KB
 // per wave and stage 10 DMA instructions: A rows [32w, 32w+32) = 4 pieces, W rows [48w, 48w+48) = 6 pieces
@@ -829,22 +857,22 @@ __global__ __launch_bounds__(512) void gemm_nt384_kernel(GemmNtArgs a) {
     constexpr bool HAS_BIAS = (EPI != DCV_EPI_PLAIN_BF16) && (EPI != DCV_EPI_GELU_BWD_BF16);
     static_assert(EPI != DCV_EPI_PATCH, "the tokeniser epilogue stays on the 256 x 128 kernel");
     constexpr bool LN = (EPI == DCV_EPI_RESID_LN);
-    constexpr int S = LN ? 0 : 3 * nt_stores_per_wave<LN ? DCV_EPI_BIAS_RESID_F32 : EPI>();  // stores one wave issues in a full tile's epilogue
+    constexpr int S1 = LN ? 0 : 3 * nt_stores_per_wave<LN ? DCV_EPI_BIAS_RESID_F32 : EPI>() / 4;  // stores one wave issues per 16-row block of a full tile's epilogue
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 1, wn = wave & 1;
     const bool late = (wave >> 2) != 0;  // waves w and w + 4 share a SIMD
     const int tiles_n = a.N / N3_BN;
-    const int tiles_m = (a.M + N3_BM - 1) / N3_BM;
-    const int total = tiles_m * tiles_n;
+    const int total = a.tiles_m * tiles_n;
     const int G = gridDim.x;
     const int pos = ((G & 7) == 0) ? (blockIdx.x & 7) * (G >> 3) + (blockIdx.x >> 3) : blockIdx.x;
 
     const unsigned smem_base = __builtin_amdgcn_readfirstlane(lds_addr(smem));
     const unsigned dmaA = 32 * wave * 128, dmaW = N3_A_BYTES + 48 * wave * 128;  // wave-uniform byte offsets in a stage
     const int nk = a.K / N3_BK;
+    __builtin_assume(nk >= 1);  // the host entries refuse K < 64: without this hipcc keeps the k-loop's entry test as a 0 / 1 flag in a VGPR it spills
     const int r16 = lane & 15, kg = lane >> 4;  // 16x16x32 fragments: row / column r16, k-chunk kg (8 elements)
-    const int rowA = (wm * 64 + r16) * 128, rowW = N3_A_BYTES + (wn * 192 + r16) * 128;  // + 16 i / 16 j rows
+    const int rowA = (wm * 64 + r16) * 128, rowW = N3_A_BYTES + (wn * 192 + r16) * 128;  // + 16 i / 16 j rows (a 192-row tile: wm * 48, a scalar step back)
     int fA0, fA1, fW0, fW1;  // per-lane fragment read offsets inside a stage: operand x k-step
     {
         const int co0 = (kg ^ swz64n(r16)) << 4;
@@ -857,25 +885,34 @@ __global__ __launch_bounds__(512) void gemm_nt384_kernel(GemmNtArgs a) {
     // Pieces q and q + 2 of a wave are 16 rows apart and share their swizzle (swz64n(row) = (row >> 1) & 7 has period 16 rows), so two per-lane
     // offsets per operand serve all pieces: the 16-row steps go into the SCALAR base (6 VGPRs less than one offset per piece, in a kernel that
     // holds 192 accumulators — the residual + LayerNorm epilogue spilled exactly these offsets and reloaded them inside the k-loop)
+    // They are set up again behind every epilogue, from a lane id hipcc cannot trace back: an epilogue needs them only for the next tile's first
+    // stage, which it issues at its top, so they are dead through the rest of it (the residual + LayerNorm epilogue spilled one of them across itself)
     unsigned voffA[2], voffW[2];
+    auto set_voff = [&]() {
+        const int ln = lane_id_here();
 #pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        const int rowa = 32 * wave + 8 * q + (lane >> 3), roww = 48 * wave + 8 * q + (lane >> 3);
-        voffA[q] = (unsigned)(((size_t)rowa * a.lda + (((lane & 7) ^ swz64n(rowa)) * 8)) * 2);
-        voffW[q] = (unsigned)(((size_t)roww * a.ldw + (((lane & 7) ^ swz64n(roww)) * 8)) * 2);
-    }
-    auto issue = [&](int m0_, int n0_, int kt, unsigned stage_base) {
+        for (int q = 0; q < 2; ++q) {
+            const int rowa = 32 * wave + 8 * q + (ln >> 3), roww = 48 * wave + 8 * q + (ln >> 3);
+            voffA[q] = (unsigned)(((size_t)rowa * a.lda + (((ln & 7) ^ swz64n(rowa)) * 8)) * 2);
+            voffW[q] = (unsigned)(((size_t)roww * a.ldw + (((ln & 7) ^ swz64n(roww)) * 8)) * 2);
+        }
+    };
+    set_voff();
+    // h_: the tile's height.  A 192-row stage is the first 192 rows of the same LDS image: waves 0-5 issue their four pieces as in a 256-row
+    // stage, waves 6-7 have no A rows (their vmcnt waits count what they issued themselves, so nothing else changes)
+    auto issue = [&](int m0_, int n0_, int h_, int kt, unsigned stage_base) {
         const int m0 = __builtin_amdgcn_readfirstlane(m0_), n0 = __builtin_amdgcn_readfirstlane(n0_);  // uniform by construction
+        const int h = __builtin_amdgcn_readfirstlane(h_);
         const bf16_t* ab = a.A + (size_t)m0 * a.lda + kt * N3_BK;  // scalar
         const bf16_t* wb = a.W + (size_t)n0 * a.ldw + kt * N3_BK;
-        if (m0 + N3_BM <= a.M) {
+        const bool has_rows = 32 * wave < h;
+        if (has_rows && m0 + h <= a.M) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) glds16s(ab + (size_t)(q >> 1) * 16 * a.lda, voffA[q & 1], stage_base + dmaA + q * 1024);
-        } else {
-            // the lane id goes through an opaque move: otherwise hipcc hoists these offsets to the top of EVERY tile, spills
+        } else if (has_rows) {
+            // the lane id is recomputed here by an opaque statement: otherwise hipcc hoists these offsets to the top of EVERY tile, spills
             // them, and the reload's s_waitcnt vmcnt(0) there drains the previous tile's epilogue stores
-            int ln = lane;
-            asm volatile("" : "+v"(ln));
+            const int ln = lane_id_here();
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int row = 32 * wave + 8 * q + (ln >> 3);
@@ -887,19 +924,30 @@ __global__ __launch_bounds__(512) void gemm_nt384_kernel(GemmNtArgs a) {
         for (int q = 0; q < 6; ++q) glds16s(wb + (size_t)(q >> 1) * 16 * a.ldw, voffW[q & 1], stage_base + dmaW + q * 1024);
     };
 
-    // tile order: round k, workgroup w -> tile k*G + pos(w)
+    // tile order: round k, workgroup w -> tile k*G + pos(w); row tile tm = L / tiles_n starts at 256 tm (tm < n256) or at
+    // 256 n256 + 192 (tm - n256): the 192-row tiles are the last ones, so they land in the last round(s) (dcv_gemm_nt384_plan)
+    auto tile_at = [&](int L_, int& m0_, int& n0_, int& h_) {
+        const int tm = L_ / tiles_n, s192 = tm - a.n256;
+        m0_ = s192 < 0 ? tm * N3_BM : a.n256 * N3_BM + s192 * 192;
+        h_ = s192 < 0 ? N3_BM : 192;
+        n0_ = (L_ - tm * tiles_n) * N3_BN;
+    };
     int L = pos < total ? pos : -1;
     int Lnext = (L >= 0 && L + G < total) ? L + G : -1;
     if (L < 0) return;
-    int m0 = (L / tiles_n) * N3_BM, n0 = (L % tiles_n) * N3_BN;
+    int m0, n0, h;
+    tile_at(L, m0, n0, h);
     int g = 0;  // global stage counter: stage g lives in buffer g & 1
-    issue(m0, n0, 0, smem_base);
-    bool stores_behind = false;
+    issue(m0, n0, h, 0, smem_base);
+    int stores_behind = 0;  // row blocks per wave (RB) of the previous tile when its S1 * RB epilogue stores were issued after this tile's first stage
 
-    for (;;) {
-        f32x4 acc[4][12];  // wave tile 64 x 192 = 4 x 12 MFMA tiles of 16 x 16
+    // one tile of 64 RB rows (RB = 4 or 3 row blocks of 16 per wave): accumulator clear, k-loop, epilogue; false after the workgroup's last tile
+    auto tile = [&](auto rbc) __attribute__((always_inline)) -> bool {
+        constexpr int RB = decltype(rbc)::value;
+        constexpr int H = 64 * RB;
+        f32x4 acc[RB][12];  // wave tile 16 RB x 192 = RB x 12 MFMA tiles of 16 x 16
 #pragma unroll
-        for (int i = 0; i < 4; ++i)
+        for (int i = 0; i < RB; ++i)
 #pragma unroll
             for (int j = 0; j < 12; ++j)
 #pragma unroll
@@ -907,45 +955,47 @@ __global__ __launch_bounds__(512) void gemm_nt384_kernel(GemmNtArgs a) {
 
 #pragma clang loop unroll(disable)  // also keeps hipcc from peeling the first iteration (the peeled copy spilled)
         for (int kt = 0; kt < nk; ++kt, ++g) {
-            // stage kt landed once only younger operations are outstanding: for kt == 0 the previous tile's S epilogue
-            // stores (issued after this tile's first stage); afterwards nothing of ours is younger than the stage
-            if (kt == 0 && stores_behind) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(S) : "memory");
+            // stage kt landed once only younger operations are outstanding: for kt == 0 the previous tile's epilogue stores
+            // (issued after this tile's first stage; their number goes with THAT tile's height); afterwards nothing of ours is younger than the stage
+            if (kt == 0 && stores_behind == 4) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * S1) : "memory");
+            else if (kt == 0 && stores_behind == 3) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * S1) : "memory");
             else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();  // stage g visible to all; all waves are done reading buffer (g+1)&1
             // (issuing half the waves' pieces between the two k-steps, as gemm_nt_kernel does, measured 3-5 % slower here: with two
             // stages the late pieces have half a stage to land)
             const char* st = smem + (g & 1) * N3_STAGE_BYTES;
-            // 24 steps (2 k-steps of 32 x 12 column blocks) of 4 MFMAs; the W fragment of step s + 2 is read at step s (ring of 3),
-            // the 4 A fragments of the second k-step replace those of the first one by one behind their last MFMA.  The order
+            // 24 steps (2 k-steps of 32 x 12 column blocks) of RB MFMAs; the W fragment of step s + 2 is read at step s (ring of 3),
+            // the RB A fragments of the second k-step replace those of the first one by one behind their last MFMA.  The order
             // is pinned (sched_barrier): left alone, hipcc hoists all 16 reads of a k-step and spills accumulators (192 of the
             // 256 registers a wave has at 8 waves per workgroup are accumulators).
             // k-step 0: chunk kg; k-step 1: chunk 4 + kg = co0 ^ 64.  swz64n(16 i + r16) is the same for every i.  The four per-lane
             // bases (A / W x k-step) are opaque values, so every fragment read is base + immediate (left to itself hipcc built one
             // address register per column block for the second k-step — twelve registers it then spilled around the loop)
-            const char* const pA0 = st + fA0;
-            const char* const pA1 = st + fA1;
+            const char* const stA = st - (4 - RB) * wm * 16 * 128;  // a wave's rows start at 16 RB wm: a scalar step, the per-lane bases stay
+            const char* const pA0 = stA + fA0;
+            const char* const pA1 = stA + fA1;
             const char* const pW0 = st + fW0;
             const char* const pW1 = st + fW1;
             auto rdW = [&](int s2) { return as_bf16x8(lds_read128(s2 >= 12 ? pW1 : pW0, (s2 % 12) * 16 * 128)); };
-            bf16x8 af[4], wq[3];
+            bf16x8 af[RB], wq[3];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) af[i] = as_bf16x8(lds_read128(pA0, i * 16 * 128));
+            for (int i = 0; i < RB; ++i) af[i] = as_bf16x8(lds_read128(pA0, i * 16 * 128));
             wq[0] = rdW(0);
             wq[1] = rdW(1);
             __builtin_amdgcn_sched_barrier(0);
-            if (kt + 1 < nk && (DCV_N3_EARLY_AT < 0 || late)) issue(m0, n0, kt + 1, smem_base + ((g + 1) & 1) * N3_STAGE_BYTES);
+            if (kt + 1 < nk && (DCV_N3_EARLY_AT < 0 || late)) issue(m0, n0, H, kt + 1, smem_base + ((g + 1) & 1) * N3_STAGE_BYTES);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int s2 = 0; s2 < 24; ++s2) {
                 if (s2 + 2 < 24) wq[(s2 + 2) % 3] = rdW(s2 + 2);
 #pragma unroll
-                for (int i = 0; i < 4; ++i) {
+                for (int i = 0; i < RB; ++i) {
                     acc[i][s2 % 12] = mfma16(wq[s2 % 3], af[i], acc[i][s2 % 12]);  // operands swapped: transposed tile (register epilogue)
                     if (s2 == 11) af[i] = as_bf16x8(lds_read128(pA1, i * 16 * 128));
                 }
                 __builtin_amdgcn_sched_barrier(0);
                 if (DCV_N3_EARLY_AT >= 0 && s2 == DCV_N3_EARLY_AT) {
-                    if (kt + 1 < nk && !late) issue(m0, n0, kt + 1, smem_base + ((g + 1) & 1) * N3_STAGE_BYTES);
+                    if (kt + 1 < nk && !late) issue(m0, n0, H, kt + 1, smem_base + ((g + 1) & 1) * N3_STAGE_BYTES);
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
@@ -956,21 +1006,22 @@ __global__ __launch_bounds__(512) void gemm_nt384_kernel(GemmNtArgs a) {
         // ---- epilogue straight from the accumulators, overlapped with the first stage of the next tile (into the other buffer) ----
         const int Ln = Lnext;
         const bool has_next = Ln >= 0;
-        const int m0n = has_next ? (Ln / tiles_n) * N3_BM : 0, n0n = has_next ? (Ln % tiles_n) * N3_BN : 0;
+        int m0n = 0, n0n = 0, hn = N3_BM;  // the next tile may have the other height
+        if (has_next) tile_at(Ln, m0n, n0n, hn);
         Lnext = (has_next && Ln + G < total) ? Ln + G : -1;
-        const bool full = (m0 + N3_BM <= a.M);
-        const int m_w = m0 + wm * 64, n_w = n0 + wn * 192;
-        // the lane id goes through an opaque move: otherwise hipcc hoists the epilogue's per-lane row / column offsets above the k-loop,
-        // where 192 accumulators are live, spills them, and reloads DMA offsets from scratch inside the loop (a scratch load is a
-        // vector-memory operation: its wait drains the ring)
-        int ln = lane;
-        asm volatile("" : "+v"(ln));
+        const bool full = (m0 + H <= a.M);
+        const int m_w = m0 + wm * 16 * RB, n_w = n0 + wn * 192;
+        // the lane id is recomputed by an opaque statement: otherwise hipcc hoists the epilogue's per-lane row / column offsets above the
+        // k-loop, where 192 accumulators are live, spills them, and reloads DMA offsets from scratch inside the loop (a scratch load is a
+        // vector-memory operation: its wait drains the ring).  Recomputed, not copied from threadIdx.x: a copy keeps that register alive across
+        // the k-loop, and the residual + LayerNorm instantiation spilled it (16 bytes of scratch, reloaded behind a vmcnt(0) in the epilogue).
+        const int ln = lane_id_here();
         const int r16e = ln & 15, kge = ln >> 4;
         if constexpr (LN) {
             // residual + LayerNorm from the accumulators; the statistics cross the two column halves through the ring buffer the last k
             // stage lived in (free until the next tile's second stage is issued)
-            nt384_resid_ln_epilogue(a, acc, m0, wm, wn, ln, smem + ((g + 1) & 1) * N3_STAGE_BYTES, [&]() {
-                if (has_next) issue(m0n, n0n, 0, smem_base + (g & 1) * N3_STAGE_BYTES);
+            nt384_resid_ln_epilogue<RB>(a, acc, m0, wm, wn, ln, smem + ((g + 1) & 1) * N3_STAGE_BYTES, [&]() {
+                if (has_next) issue(m0n, n0n, hn, 0, smem_base + (g & 1) * N3_STAGE_BYTES);
             });
         } else {
             // column blocks of 64 x row blocks of 16
@@ -981,16 +1032,26 @@ __global__ __launch_bounds__(512) void gemm_nt384_kernel(GemmNtArgs a) {
                 nt_epilogue_block<EPI, 1, 4, 12, J0>(a, acc, m_w, n_w + 16 * J0, r16e, kge, bz, between);
             };
             block(std::integral_constant<int, 0>{}, [&]() {
-                if (has_next) issue(m0n, n0n, 0, smem_base + (g & 1) * N3_STAGE_BYTES);
+                if (has_next) issue(m0n, n0n, hn, 0, smem_base + (g & 1) * N3_STAGE_BYTES);
             });
             block(std::integral_constant<int, 4>{}, []() {});
             block(std::integral_constant<int, 8>{}, []() {});
         }
-        if (!has_next) break;
-        stores_behind = full && !LN;  // the LayerNorm epilogue's store count is not fixed (row predicates): its next tile starts behind vmcnt(0)
+        if (!has_next) return false;
+        stores_behind = (full && !LN) ? RB : 0;  // the LayerNorm epilogue's store count is not fixed (row predicates): its next tile starts behind vmcnt(0)
         m0 = m0n;
         n0 = n0n;
+        h = hn;
         L = Ln;
+        set_voff();
+        return true;
+    };
+    for (;;) {
+        if (h == N3_BM) {
+            if (!tile(std::integral_constant<int, 4>{})) break;
+        } else {
+            if (!tile(std::integral_constant<int, 3>{})) break;
+        }
     }
 }
 
@@ -1579,6 +1640,45 @@ extern "C" int dcv_gemm_nt_pick(int M, int N, int K, int epilogue, int tile) {
     return (10 * rw * (K >= 1536 ? 23 : 25) < 100 * rn) ? DCV_TILE_WIDE : DCV_TILE_NARROW;
 }
 
+// Row-tile plan of gemm_nt384_kernel (host logic, no GPU call).  The kernel deals its tiles statically, tile L = k * grid + pos in round k, so a
+// launch lasts as long as the workgroup with the most rows.  With 256-row tiles only, M = 100 416 on 256 workgroups is 393 tiles: two rounds for
+// 1.53 rounds of work.  The plan makes the LAST row tiles 192 rows high (3 of a wave's 4 row blocks; nothing else about a tile changes), so the
+// last round(s) are shorter: rows [0, 256 n256) in 256-row tiles, the rest in n192 = ceil((M - 256 n256) / 192) tiles of 192 rows.
+//   * Heights fall along the walk, so workgroup 0 walks the most rows: 256 c + 192 (R - c) with R = ceil(tiles / grid) rounds, of which
+//     c = ceil(n256 tiles_n / grid) start on a 256-row tile.
+//   * No workgroup may walk more tiles than before: R stays ceil(old tiles / grid).  Lowering n256 only adds tiles, so the smallest n256 that
+//     still fits R rounds gives the smallest c; among the plans with that c the one with the MOST 256-row tiles is taken (fewest tiles, each of
+//     which re-reads its W panel): n256 = floor(c grid / tiles_n).
+//   * Where that does not lower the largest walk (one round or less, or rows that mixed rounds cannot cover) the answer is the old plan, n192 = 0.
+// Headline: M = 100 416, grid 256 -> 256 + 182 tiles, 448 rows per workgroup instead of 512 (grid 248: 248 + 193, 448).
+// -DDCV_N3_BALANCE=0: always the old plan (the A/B build).
+#ifndef DCV_N3_BALANCE
+#define DCV_N3_BALANCE 1
+#endif
+extern "C" int dcv_gemm_nt384_plan(int M, int N, int grid, int* n256, int* n192) {
+    if (!n256 || !n192) return DCV_ERR_NULL;
+    if (M <= 0 || N <= 0 || (N % N3_BN) != 0 || grid <= 0) return DCV_ERR_SHAPE;
+    const long tn = N / N3_BN, G = grid;
+    const long old_m = (M + N3_BM - 1) / N3_BM;
+    *n256 = (int)old_m;
+    *n192 = 0;
+    const long R = (old_m * tn + G - 1) / G;
+    if (!DCV_N3_BALANCE || R <= 1) return DCV_OK;
+    auto rest192 = [&](long a) { return a * N3_BM >= M ? 0L : (M - a * N3_BM + 191) / 192; };
+    long lo = 0, hi = old_m;  // smallest n256 whose tiles fit R rounds (the tile count falls as n256 grows; old_m fits)
+    while (lo < hi) {
+        const long mid = (lo + hi) / 2;
+        if ((mid + rest192(mid)) * tn <= R * G) hi = mid;
+        else lo = mid + 1;
+    }
+    const long c = (lo * tn + G - 1) / G;
+    const long a = std::min(c * G / tn, old_m);
+    if (c >= R || rest192(a) == 0) return DCV_OK;
+    *n256 = (int)a;
+    *n192 = (int)rest192(a);
+    return DCV_OK;
+}
+
 extern "C" int dcv_gemm_tn_pick(int M, int P, int Q, int tile) {
     (void)M;
     if (tile < DCV_TILE_AUTO || tile > DCV_TILE_WIDE) return DCV_ERR_SHAPE;
@@ -1603,8 +1703,8 @@ extern "C" int dcv_gemm_nt_ex(const void* A, int lda, const void* W, int ldw, in
     hipStream_t s = (hipStream_t)stream;
     // 256 x 384 tiles where they pay (measured, M = 100 416, against the 256 x 128 kernel): N = 1152 K = 384: 121 -> 107 us;
     // N = 1536 K = 384 + GELU: 238 -> 218; N = 384 K = 1536: 192 -> 184 (+residual), 154 -> 138 (plain); but N = 384 K = 384:
-    // 96 -> 101 (393 tiles on 256 CUs: two rounds for 1.5 rounds of work), and the GELU-backward epilogue (N = 1536, HBM-heavy:
-    // 616 MB in + out) 212 -> 220.  tile = DCV_TILE_WIDE forces the 256 x 384 kernel wherever it is legal, DCV_TILE_NARROW never uses it.
+    // 96 -> 101 (393 tiles on 256 CUs: two rounds for 1.5 rounds of work — measured before dcv_gemm_nt384_plan made the second round's tiles 192
+    // rows high; the choice was not re-tuned), and the GELU-backward epilogue (N = 1536, HBM-heavy: 616 MB in + out) 212 -> 220.  tile = DCV_TILE_WIDE forces the 256 x 384 kernel wherever it is legal, DCV_TILE_NARROW never uses it.
     int pick = dcv_gemm_nt_pick(M, N, K, epilogue, tile);
     if (pick < 0) return pick;
 #if DCV_NT_WS
@@ -1645,6 +1745,9 @@ extern "C" int dcv_gemm_nt_ex(const void* A, int lda, const void* W, int ldw, in
     if (pick == DCV_TILE_WIDE) {
         int g3 = ((M + N3_BM - 1) / N3_BM) * (N / N3_BN);
         if (g3 > cap) g3 = cap;
+        int n192;
+        dcv_gemm_nt384_plan(M, N, g3, &a.n256, &n192);  // the grid is min(tiles, cap) under either plan: a plan with 192-row tiles has more than one round
+        a.tiles_m = a.n256 + n192;
         DCV_NT_CASES(gemm_nt384_kernel, g3)
             default:
                 return DCV_ERR_UNSUPPORTED;
@@ -1693,6 +1796,9 @@ extern "C" int dcv_gemm_nt_resid_ln(const void* A, int lda, const void* W, int l
                  gamma, beta, mean, rstd, eps};
     int g3 = (M + N3_BM - 1) / N3_BM;
     if (g3 > cap) g3 = cap;
+    int n192;
+    dcv_gemm_nt384_plan(M, N, g3, &a.n256, &n192);
+    a.tiles_m = a.n256 + n192;
     hipLaunchKernelGGL(gemm_nt384_kernel<DCV_EPI_RESID_LN>, dim3(g3), dim3(512), 0, (hipStream_t)stream, a);
     DCV_LAUNCH_CHECK();
     return DCV_OK;

@@ -22,6 +22,7 @@ _SIGS = {
     "dcv_gemm_nt": ([_vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _vp], _i),
     "dcv_gemm_nt_ex": ([_vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _vp], _i),
     "dcv_gemm_nt_pick": ([_i, _i, _i, _i, _i], _i),
+    "dcv_gemm_nt384_plan": ([_i, _i, _i, _vp, _vp], _i),
     "dcv_gemm_nt_resid_ln": ([_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _f, _vp, _i, _vp, _vp, _i, _vp], _i),
     "dcv_gemm_tn_pick": ([_i, _i, _i, _i], _i),
     "dcv_gemm_tn_acc": ([_vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp], _i),

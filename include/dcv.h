@@ -83,6 +83,10 @@ int dcv_gemm_nt_resid_ln(const void* A, int lda, const void* W, int ldw, int M, 
 /* the variant (DCV_TILE_NARROW / DCV_TILE_WIDE) the *_ex forms launch for a problem — pure functions of their arguments */
 int dcv_gemm_nt_pick(int M, int N, int K, int epilogue, int tile);
 int dcv_gemm_tn_pick(int M, int P, int Q, int tile);
+/* row-tile plan of the 256 x 384 NT kernel (DCV_TILE_WIDE, dcv_gemm_nt_resid_ln) for M rows, N % 384 == 0 columns and `grid` workgroups — host
+ * logic, no GPU call: rows [0, 256 n256) in 256-row tiles, the rest in n192 tiles of 192 rows, which fall into the last round(s) of the
+ * static walk (tile = round * grid + workgroup) and shorten them.  n192 = 0 wherever that would not lower the most rows a workgroup walks. */
+int dcv_gemm_nt384_plan(int M, int N, int grid, int* n256, int* n192);
 int dcv_gemm_tn_acc_ex(const void* Y, int ldy, const void* X, int ldx, int M, int P, int Q, float* dW, int lddw, float* dbias,
                        int tile, void* stream);
 /* DETERMINISTIC form (the reference trains with cudnn.deterministic = True, utils.py:394-401): the workgroups that split the token
