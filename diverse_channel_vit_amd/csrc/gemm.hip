@@ -1696,6 +1696,15 @@ extern "C" int dcv_gemm_nt_ex(const void* A, int lda, const void* W, int ldw, in
     if ((lda % 8) || (ldw % 8) || (ldo % 8) || ((uintptr_t)A & 15) || ((uintptr_t)W & 15) || ((uintptr_t)out & 15)) return DCV_ERR_ALIGN;
     if (grid_cap < 0 || tile < DCV_TILE_AUTO || tile > DCV_TILE_AUTO_WS) return DCV_ERR_SHAPE;
     if (epilogue == DCV_EPI_BIAS_RESID_F32 && aux2 && (T <= 0 || (M % T) != 0)) return DCV_ERR_SHAPE;  // per-sample branch scale: T rows per sample
+    // A row stride below the row's width would make rows overlap silently; the strides of the optional buffers count only where the epilogue
+    // uses them (callers pass 0 with a null pointer).  out2: bf16 (GELU) or fp32 (PATCH); aux: fp32 residual / embedding rows (PATCH: aux2 shares
+    // ldaux) or the bf16 saved GELU'(z) — all of them move in 16-byte pieces.
+    if (lda < K || ldw < K || ldo < N) return DCV_ERR_SHAPE;
+    const bool uses_out2 = out2 && (epilogue == DCV_EPI_BIAS_GELU_BF16 || epilogue == DCV_EPI_PATCH);
+    const bool uses_aux = aux && (epilogue == DCV_EPI_BIAS_RESID_F32 || epilogue == DCV_EPI_GELU_BWD_BF16 || epilogue == DCV_EPI_PATCH);
+    if ((uses_out2 && ldo2 < N) || (uses_aux && ldaux < N)) return DCV_ERR_SHAPE;
+    if ((uses_out2 && (ldo2 % (epilogue == DCV_EPI_PATCH ? 4 : 8))) || (uses_aux && (ldaux % (epilogue == DCV_EPI_GELU_BWD_BF16 ? 8 : 4))))
+        return DCV_ERR_ALIGN;
     // persistent kernels: one workgroup per CU walks the tiles; grid_cap (> 0) lowers the number of workgroups — the data-parallel
     // backward leaves CUs to RCCL's kernels this way (dichavit.py), tests force multi-round walks on small problems
     const int cap = grid_cap > 0 ? grid_cap : dcv_cu_count();
@@ -1787,6 +1796,7 @@ extern "C" int dcv_gemm_nt_resid_ln(const void* A, int lda, const void* W, int l
     if (!A || !W || !bias || !resid || !x_out || !gamma || !beta || !u_out || !mean || !rstd) return DCV_ERR_NULL;
     if (M <= 0 || K <= 0 || (K % 64) != 0 || grid_cap < 0) return DCV_ERR_SHAPE;
     if (N != N3_BN) return DCV_ERR_UNSUPPORTED;  // the tile must span whole rows
+    if (lda < K || ldw < K || ldo < N || ldr < N || ldu < N) return DCV_ERR_SHAPE;  // rows would overlap
     if ((lda % 8) || (ldw % 8) || (ldo % 4) || (ldr % 4) || (ldu % 8) || ((uintptr_t)A & 15) || ((uintptr_t)W & 15) || ((uintptr_t)x_out & 15) ||
         ((uintptr_t)resid & 15) || ((uintptr_t)u_out & 15) || ((uintptr_t)bias & 15) || ((uintptr_t)gamma & 15) || ((uintptr_t)beta & 15))
         return DCV_ERR_ALIGN;
@@ -1836,6 +1846,7 @@ static int tn_launch(const void* Y, int ldy, const void* X, int ldx, int M, int 
                      float* ws, long ws_floats, void* stream) {
     if (!Y || !X || !dW) return DCV_ERR_NULL;
     if (M <= 0 || P <= 0 || Q <= 0 || (P % 8) || (Q % 8)) return DCV_ERR_SHAPE;
+    if (ldy < P || ldx < Q || lddw < Q) return DCV_ERR_SHAPE;  // rows would overlap
     if ((ldy % 8) || (ldx % 8) || ((uintptr_t)Y & 15) || ((uintptr_t)X & 15)) return DCV_ERR_ALIGN;
     if (tile < DCV_TILE_AUTO || tile > DCV_TILE_WIDE) return DCV_ERR_SHAPE;
     const int cus = dcv_cu_count();
@@ -1911,6 +1922,7 @@ static int tn_group_plan(const dcv_tn_item* it, int n, int M, int cus, TnGroupPl
     for (int i = 0; i < n; ++i) {
         if (!it[i].Y || !it[i].X || !it[i].dW) return DCV_ERR_NULL;
         if (it[i].P <= 0 || it[i].Q <= 0 || (it[i].P % 384) || (it[i].Q % 128)) return DCV_ERR_UNSUPPORTED;
+        if (it[i].ldy < it[i].P || it[i].ldx < it[i].Q || it[i].lddw < it[i].Q) return DCV_ERR_SHAPE;  // rows would overlap
         if ((it[i].ldy % 8) || (it[i].ldx % 8) || ((uintptr_t)it[i].Y & 15) || ((uintptr_t)it[i].X & 15)) return DCV_ERR_ALIGN;
         pl.tiles[i] = (it[i].P / 384) * (it[i].Q / 128);
         tiles += pl.tiles[i];

@@ -40,7 +40,11 @@ extern "C" {
 int dcv_version(void);
 const char* dcv_error_string(int code);
 
-/* C[M,N] = A[M,K] . W[N,K]^T (bf16 in, f32 accumulate) + epilogue.  K % 64 == 0, lda/ldw % 8 == 0.
+/* C[M,N] = A[M,K] . W[N,K]^T (bf16 in, f32 accumulate) + epilogue.  K % 64 == 0, N % 8 == 0.
+ * Leading dimensions (row strides in elements; every row moves in 16-byte pieces): lda, ldw >= K and ldo >= N, multiples of 8; where the epilogue
+ * uses the buffer, ldo2 >= N and ldaux >= N, multiples of 8 for bf16 (GELU's out2, GELU_BWD's aux) and of 4 for fp32 (PATCH's out2; the residual;
+ * PATCH's aux and aux2, which share ldaux).  A stride below the width is DCV_ERR_SHAPE (rows would overlap), one off its multiple DCV_ERR_ALIGN; a
+ * null optional buffer's stride is not looked at.
  * Replaces F.linear forward / input-gradient and the Conv3d patch projection (on im2col rows). */
 int dcv_gemm_nt(const void* A, int lda, const void* W, int ldw, int M, int N, int K, int epilogue, const float* bias,
                 void* out, int ldo, void* out2, int ldo2, const void* aux, int ldaux, const float* aux2, int T, int n,
@@ -66,7 +70,8 @@ int dcv_gemm_nt_ex(const void* A, int lda, const void* W, int ldw, int M, int N,
                    void* out, int ldo, void* out2, int ldo2, const void* aux, int ldaux, const float* aux2, int T, int n,
                    int grid_cap, int tile, void* stream);
 
-/* dW[P,Q] (f32) += sum_m Y[m,P] * X[m,Q] ; dbias[P] (f32, nullable) += sum_m Y[m,P].  bf16 inputs.
+/* dW[P,Q] (f32) += sum_m Y[m,P] * X[m,Q] ; dbias[P] (f32, nullable) += sum_m Y[m,P].  bf16 inputs.  P, Q % 8 == 0; ldy >= P and ldx >= Q,
+ * multiples of 8; lddw >= Q (DCV_ERR_SHAPE below the width, DCV_ERR_ALIGN off the multiple; the grouped form checks every item the same way).
  * Replaces the weight/bias gradients of nn.Linear / Conv3d (autograd of vit.py:72-74,123,142; dichavit.py:377). */
 int dcv_gemm_tn_acc(const void* Y, int ldy, const void* X, int ldx, int M, int P, int Q, float* dW, int lddw, float* dbias,
                     void* stream);
@@ -75,7 +80,7 @@ int dcv_gemm_tn_acc(const void* Y, int ldy, const void* X, int ldx, int M, int P
  *   u_out bf16 [M,N] = (x_out - mean) * rstd * gamma + beta,   mean / rstd f32 [M]   (norm2 / the next block's norm1, vit.py:397-398; eps as given)
  * = dcv_gemm_nt(DCV_EPI_BIAS_RESID_F32) + dcv_ln_fwd in one launch, without the re-read of x_out.  Statistics are centred (Chan's pairwise
  * combination), as dcv_ln_fwd's.  Returns DCV_ERR_UNSUPPORTED for N != 384.  Alignment (DCV_ERR_ALIGN otherwise): every pointer 16 bytes — u_out
- * included: its rows leave in 16-byte stores — lda, ldw, ldu multiples of 8, ldo, ldr of 4. */
+ * included: its rows leave in 16-byte stores — lda, ldw, ldu multiples of 8, ldo, ldr of 4.  lda, ldw >= K and ldo, ldr, ldu >= N, else DCV_ERR_SHAPE. */
 int dcv_gemm_nt_resid_ln(const void* A, int lda, const void* W, int ldw, int M, int N, int K, const float* bias, const float* resid, int ldr,
                          const float* branch_scale, int T, float* x_out, int ldo, const float* gamma, const float* beta, float eps,
                          void* u_out, int ldu, float* mean, float* rstd, int grid_cap, void* stream);
