@@ -36,7 +36,9 @@ def _plain(obj):
 
 
 def save_checkpoint(path: str, model, optimizer, scheduler=None, epoch: int = 0, accuracy: Optional[float] = None, config=None,
-                    scaler=None) -> None:
+                    scaler=None, averaged=None) -> None:
+    """averaged: an averaging.AveragedModel (or torch's own): its state_dict() is stored under ``averaged_params``.  Without it the file
+    is exactly what it was before that key existed."""
     state = {
         "epoch": epoch,
         "accuracy": accuracy,
@@ -47,6 +49,8 @@ def save_checkpoint(path: str, model, optimizer, scheduler=None, epoch: int = 0,
         "scaler_params": scaler.state_dict() if scaler is not None else {},
         "datetime": datetime.datetime.now().strftime("%Y-%m-%d %H:%M:%S"),
     }
+    if averaged is not None:
+        state["averaged_params"] = averaged.state_dict()
     torch.save(state, path)
 
 
@@ -60,16 +64,21 @@ def _match_prefix(params: dict, model) -> dict:
     return params
 
 
-def load_checkpoint(path: str, model, optimizer=None, scheduler=None, map_location=None) -> int:
+def load_checkpoint(path: str, model, optimizer=None, scheduler=None, map_location=None, averaged=None) -> int:
     """Returns the stored epoch (trainer.py:1325-1328).  Files are read with ``weights_only=True``: a checkpoint whose
     ``config`` entry is a pickled OmegaConf object (what the reference itself writes) is refused by that loader — re-save it
-    with a plain-dict config, this function never unpickles arbitrary objects."""
+    with a plain-dict config, this function never unpickles arbitrary objects.  averaged: the AveragedModel to restore from the file's
+    ``averaged_params`` (a file without that key cannot restore one: ValueError); without it the key is ignored."""
     state = torch.load(path, map_location=map_location, weights_only=True)
     model.load_state_dict(_match_prefix(state["model_params"], model))
     if optimizer is not None and state.get("optimizer_params") is not None:
         optimizer.load_state_dict(state["optimizer_params"])
     if scheduler is not None and state.get("scheduler_params") is not None:
         scheduler.load_state_dict(state["scheduler_params"])
+    if averaged is not None:
+        if state.get("averaged_params") is None:
+            raise ValueError(f"{path} holds no averaged_params: it was saved without averaged=...")
+        averaged.load_state_dict(state["averaged_params"])
     return int(state.get("epoch", 0))
 
 

@@ -17,7 +17,10 @@ import torch
 
 class GraphedTrainStep:
     def __init__(self, model, optimizer, chunk_name: str = "train", training_chunks: Optional[str] = None,
-                 loss_fn: Optional[Callable] = None, extra_loss_lambda: float = 1.0, warmup: int = 2):
+                 loss_fn: Optional[Callable] = None, extra_loss_lambda: float = 1.0, warmup: int = 2, averager=None):
+        """averager: an averaging.AveragedModel whose update_parameters(model) runs right after the optimizer step, INSIDE the captured
+        graph (SWAD, trainer.py:957-959; an EMA of the weights): its count is read on the device, so every replay averages with the
+        live weight.  The warm-up steps count as updates, as they count as optimizer steps."""
         if not getattr(optimizer, "capturable", False):
             raise ValueError("GraphedTrainStep needs HipAdamW(capturable=True)")
         if model.training and model.feature_extractor.patch_embed.enable_sample and model.hcs_sampler is None:
@@ -33,6 +36,7 @@ class GraphedTrainStep:
         self.loss_fn = loss_fn or torch.nn.CrossEntropyLoss()
         self.lam = extra_loss_lambda
         self.warmup = warmup
+        self.averager = averager
         self.graph = None
         self.capture_two_streams = False  # see _capture
         self.static_x = self.static_y = self.static_loss = self.static_out = self.static_extra = None
@@ -44,6 +48,8 @@ class GraphedTrainStep:
         loss = self.loss_fn(out, self.static_y) + extra * self.lam
         loss.backward()
         self.opt.step()
+        if self.averager is not None:
+            self.averager.update_parameters(self.model)
         self.static_out, self.static_extra = out.detach(), extra.detach()  # valid after every replay, like the loss
         return loss
 

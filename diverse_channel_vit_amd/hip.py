@@ -73,6 +73,7 @@ _SIGS = {
     "dcv_adamw_set_hyper": ([_vp, _f, _f, _f, _f, _f, _i, _f, _vp], _i),
     "dcv_adamw_set_hyper_groups": ([_vp, _vp, _vp, _i, _f, _vp], _i),
     "dcv_adamw_groups": ([_vp, _vp, _vp, _vp, _l, _vp, _vp, _i, _vp, _i, _vp], _i),
+    "dcv_avg_update": ([_vp, _vp, _l, _i, _f, _l, _vp, _i, _vp], _i),
     "dcv_cast_bf16": ([_vp, _vp, _l, _vp], _i),
     "dcv_cast_transpose_bf16": ([_vp, _vp, _vp, _i, _i, _vp], _i),
     "dcv_sumsq_acc": ([_vp, _l, _vp, _vp], _i),
@@ -516,6 +517,22 @@ def adamw_set_hyper_groups(hyper_dev, rows, steps, grad_scale=1.0):
 def adamw_groups(p, g, m, v, n, seg_end4, seg_group, n_seg, hyper_dev, n_groups):
     _check(load().dcv_adamw_groups(_p(p), _p(g), _p(m), _p(v), n, _p(seg_end4), _p(seg_group), n_seg, _p(hyper_dev), n_groups, _stream()),
            "dcv_adamw_groups")
+
+
+AVG_SWA, AVG_EMA = 0, 1  # include/dcv.h DCV_AVG_*
+
+
+def avg_update(avg, p, n, mode, ema_weight=0.0, n_averaged=0, n_averaged_dev=None, grid_cap=0):
+    """avg[:n] <- lerp(avg[:n], p[:n], w) in one launch (include/dcv.h: dcv_avg_update).  n_averaged_dev: an int64 device word holding the
+    count of updates so far (read, never written); without it the count is n_averaged."""
+    _req(avg, torch.float32, "avg"); _req(p, torch.float32, "p")
+    if avg.numel() < n or p.numel() < n:
+        raise ValueError("avg_update: avg and p hold at least n floats")
+    if n_averaged_dev is not None:
+        _req(n_averaged_dev, torch.int64, "n_averaged_dev")
+    with _timer(lambda: ("avg_update_kernel", f"n{n}", 0.0, None, 12.0 * n)):
+        rc = load().dcv_avg_update(_p(avg), _p(p), n, int(mode), float(ema_weight), int(n_averaged), _p(n_averaged_dev), int(grid_cap), _stream())
+    _check(rc, "dcv_avg_update")
 
 
 def cast_bf16(src, dst, n):

@@ -277,6 +277,21 @@ int dcv_adamw_set_hyper_groups(float* hyper_dev, const float* rows_host, const i
  * that row, bit for bit. */
 int dcv_adamw_groups(float* p, const float* g, float* m, float* v, long n, const int* seg_end4, const int* seg_group, int n_seg,
                      const float* hyper_dev, int n_groups, void* stream);
+/* Weight averaging over the flat parameter arena (csrc/avg.hip): avg[i] <- lerp(avg[i], p[i], w) for i < n in ONE launch — SWA / SWAD and
+ * EMA of the weights (torch.optim.swa_utils.AveragedModel.update_parameters; the reference trainer's train.swa / train.swad, trainer.py:810-812,
+ * 957-959).  The count of updates so far is read from the device word *n_averaged_dev when that is not NULL (n_averaged is then ignored; the
+ * kernel never writes the word: the caller bumps it, stream-ordered, so a captured step replays with the live count), else it is n_averaged.
+ *   count == 0: w = 1 in both modes (the first update copies);  DCV_AVG_SWA: w = 1.0f / (float)(count + 1), correctly rounded;
+ *   DCV_AVG_EMA: w = ema_weight (pass (float)(1 - decay)).
+ * Element: w == 1: avg = p bit for bit; w < 0.5: fmaf(w, p - avg, avg); else fmaf(-(p - avg), 1 - w, p) (ATen's two-sided lerp).  No atomics:
+ * bitwise reproducible; p is read only; avg and p must not overlap.  grid_cap > 0 caps the number of workgroups (0: the product's cap).
+ * Checked in this order, before any HIP call: avg / p NULL -> DCV_ERR_NULL; n < 0 -> DCV_ERR_SHAPE; avg / p not 16-byte (n_averaged_dev not
+ * 8-byte) aligned -> DCV_ERR_ALIGN; an unknown mode -> DCV_ERR_UNSUPPORTED; ema_weight outside [0, 1] or NaN, n_averaged < 0 (when it is used),
+ * grid_cap < 0 -> DCV_ERR_SHAPE.  n == 0 succeeds and launches nothing. */
+#define DCV_AVG_SWA 0
+#define DCV_AVG_EMA 1
+int dcv_avg_update(float* avg, const float* p, long n, int mode, float ema_weight, long n_averaged, const long long* n_averaged_dev,
+                   int grid_cap, void* stream);
 /* Gradient clipping (trainer.py:1003-1004 -> torch.nn.utils.clip_grad_norm_, L2): dcv_sumsq_acc adds sum(x^2) of a flat fp32
  * range to the device scalar *acc (zero it first; call once per gradient buffer); dcv_clip_scale multiplies a range by
  * min(1, max_norm / (sqrt(*sumsq_dev) + 1e-6)).  Everything stays on the device: no host sync, graph-capturable. */
