@@ -335,6 +335,29 @@ class ChannelVisionTransformer(_Holder):
                                "copies); this ChannelVisionTransformer is not linked to one")
         return owner._probe_layers(x, chunk, training_chunks, new_channel_init, blocks, pool)
 
+    def get_channel_attention(self, x, extra_tokens={}, n=1, *, chunk="", training_chunks=None, new_channel_init=None, queries="channel"):
+        """Which channels does the model look at, and from where: the softmax attention of the last `n` blocks reduced to channel granularity, as a
+        list of fp32 tensors on x's device, detached (an inspection API: no gradient), earliest block first.  No counterpart in the reference, whose
+        users reduce get_last_selfattention's [B, H, N, N] map themselves, one block per call; here the reduction happens inside the kernel
+        (dcv_attn_channel_mass, from the forward's qkv and LSE), any set of blocks is captured in one forward and no N x N matrix is ever written.
+        The tokens are prepared as forward() prepares them (see get_intermediate_layers, whose parameters these are); blocks after the last
+        requested one do not run.
+
+        The key axis falls into 1 + C segments: S_0 = {CLS}, S_{1+c} = the n_p patch tokens of channel c, channels in this forward's token order
+        (the chunk's, or in train mode the HCS subset's).
+        n: an int, 1 <= n <= depth, or a sequence of distinct block indices (negative counts from the end); entries come back in block order.
+        queries="token": each entry is [B, H, N, 1 + C] — T[b, h, q, j] = the attention mass query token q puts on segment j; every row sums to 1.
+        queries="channel": each entry is [B, H, 1 + C, 1 + C] — A[b, h, i, j] = the mean of T over the query tokens of segment i: row-stochastic,
+        row 0 is the CLS query's mass per channel.  Raises ValueError under token drop (ragged channel segments)."""
+        blocks = _parse_layers(n, len(self.blocks))
+        if queries not in ("channel", "token"):
+            raise ValueError(f"queries={queries!r}: expected 'channel' or 'token'")
+        owner = self._owner() if self._owner is not None else None
+        if owner is None:
+            raise RuntimeError("get_channel_attention runs through the DiChaViT that owns this encoder (its parameter arena and operand "
+                               "copies); this ChannelVisionTransformer is not linked to one")
+        return owner._probe_channel_attention(x, chunk, training_chunks, new_channel_init, blocks, queries)
+
     @staticmethod
     def _init_weights(m):  # dichavit.py:509-516
         if isinstance(m, nn.Linear):
@@ -873,7 +896,7 @@ class DiChaViT(nn.Module):
         return out
 
     def _run_forward(self, x, ch_idx_dev, C, E, pos_tab, want_ortho, save, keep=None, st_scale=None, st_shift=None, tok=None, probe=None,
-                     capture=None, frozen_k=None):
+                     capture=None, frozen_k=None, chan_attn=None):
         """frozen_k=k (with save): blocks < k and the tokeniser keep nothing for the backward (they run as with save=False, on the same
         kernels); st["layers"] still has one entry per block — the backward indexes it by block number — which for blocks < k holds the
         DropPath factors only.
@@ -884,7 +907,11 @@ class DiChaViT(nn.Module):
         capture=(blocks, pool): get_intermediate_layers — the same discipline; every block runs on all rows (no CLS-only tail), the final norm of
         the stream after each block of `blocks` (ascending) is launched right after that block — with save=False the stream is updated in place,
         so the capture is stream-ordered before the next block overwrites it — and the list of captures is returned after the last of them
-        instead of the state.  pool=None: [B, N, D] (dcv_ln_fwd, fp32 output); pool="channel": [B, 1 + C, D] (dcv_ln_pool_channels)."""
+        instead of the state.  pool=None: [B, N, D] (dcv_ln_fwd, fp32 output); pool="channel": [B, 1 + C, D] (dcv_ln_pool_channels).
+        chan_attn=(blocks, queries): get_channel_attention — the same discipline again (scratch operand copies, every block on all rows); a block of
+        `blocks` (ascending) runs its ordinary attention and then dcv_attn_channel_mass on its qkv and LSE — queries="channel": [B, H, 1 + C, 1 + C],
+        "token": [B, H, N, 1 + C], the key segments by (C, n) — and the list is returned right after the last of them: the rest of that block and
+        every later block never run.  Needs keep=None (whole segments)."""
         fe = self.feature_extractor
         D, H = self.dim, fe.num_heads
         P = fe.patch_size
@@ -895,7 +922,7 @@ class DiChaViT(nn.Module):
         dev = x.device
         bf, f32 = torch.bfloat16, torch.float32
         ps = bool(self.attn_prescaled)  # pre-scaled q for this forward AND its backward (kept in the saved state)
-        if probe is None and capture is None:
+        if probe is None and capture is None and chan_attn is None:
             self._refresh_operand_copies(stochastic=bool(save) and self.training and self.stochastic_weight_rounding, prescale_q=ps)
             wbuf, qbias = None, self._qbias
         else:
@@ -955,7 +982,7 @@ class DiChaViT(nn.Module):
         for bi, blk in enumerate(fe.blocks):
             L = {}
             sv = save and (fk is None or bi >= fk)  # this block's activations are kept for the backward
-            tail = self.cls_only_tail and bi == len(fe.blocks) - 1 and capture is None  # a captured last block runs on all rows
+            tail = self.cls_only_tail and bi == len(fe.blocks) - 1 and capture is None and chan_attn is None  # a captured last block runs on all rows
             dsc = drop[bi] if drop is not None else None  # (attention branch, MLP branch) factors [B] or None
             if pre_ln is not None:  # norm1 of this block came out of the previous block's fc2 + residual epilogue
                 u1, mean1, rstd1 = pre_ln
@@ -989,6 +1016,13 @@ class DiChaViT(nn.Module):
                 R = B  # rows the rest of this block works on
             else:
                 hip.attn_fwd(qkv, o, lse, B, N, H, D // H, scale, prescaled=ps)
+                if chan_attn is not None and bi in chan_attn[0]:
+                    cap = torch.empty((B, H, N, 1 + C) if chan_attn[1] == "token" else (B, H, 1 + C, 1 + C), dtype=f32, device=dev)
+                    hip.attn_channel_mass(qkv, lse, B, N, H, D // H, scale, C, n, prescaled=ps,
+                                          **{"tok" if chan_attn[1] == "token" else "ch": cap})
+                    captured.append(cap)
+                    if bi == chan_attn[0][-1]:
+                        return captured
                 o_c = None
                 xmid = torch.empty(M, D, dtype=f32, device=dev) if sv else xcur
                 R = M
@@ -1504,6 +1538,18 @@ class DiChaViT(nn.Module):
                                  "segments are ragged (pool=None returns the kept tokens)")
             return self._run_forward(tk.x, tk.ch_idx_dev, tk.C, tk.E_tok, tk.pos_tab, False, save=False, keep=tk.keep, st_scale=tk.scale,
                                      st_shift=tk.shift, tok=tk.tok, capture=(blocks, pool))
+
+    def _probe_channel_attention(self, x, chunk_name, training_chunks, new_channel_init, blocks, queries):
+        """ChannelVisionTransformer.get_channel_attention: the tokens as forward() prepares them, then blocks 0 .. blocks[-1] through
+        _run_forward's chan_attn.  DataParallel's begin_forward() is not called: no gradient leaves this path."""
+        with torch.autocast(device_type="cuda", enabled=False), torch.no_grad():
+            self._check_input(x)
+            tk = self._prepare_tokens(x, chunk_name, training_chunks, new_channel_init)
+            if tk.keep is not None:
+                raise ValueError("get_channel_attention needs every channel's n_p patch tokens: with dropout_tokens_hcs active in train mode the "
+                                 "channel segments are ragged")
+            return self._run_forward(tk.x, tk.ch_idx_dev, tk.C, tk.E_tok, tk.pos_tab, False, save=False, keep=None, st_scale=tk.scale,
+                                     st_shift=tk.shift, tok=tk.tok, chan_attn=(blocks, queries))
 
     def _ortho_from_stats(self, stats, C, n):
         """loss_fn.py:44-59 on the per-image (pos_sum, neg_sum)."""

@@ -59,6 +59,9 @@ _SIGS = {
     "dcv_attn_bwd_dkdv_rows_ps": ([_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp], _i),
     "dcv_attn_probs_rows": ([_vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp], _i),
     "dcv_attn_probs_rows_ps": ([_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp], _i),
+    "dcv_attn_channel_mass_ws_floats": ([_i, _i, _i, _i], _l),
+    "dcv_attn_channel_mass": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _i, _vp, _l, _vp], _i),
+    "dcv_attn_channel_mass_ps": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _l, _vp], _i),
     "dcv_im2col_bf16": ([_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp], _i),
     "dcv_patch_bwd": ([_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp], _i),
     "dcv_patch_dgrad": ([_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp], _i),
@@ -431,6 +434,37 @@ def attn_probs(qkv, lse, P, B, N, H, hd, scale, nq=None, prescaled=False):
         else:
             rc = load().dcv_attn_probs_rows(_p(qkv), _p(lse), _p(P), B, N, nq_, H, hd, float(scale), _stream())
     _check(rc, "dcv_attn_probs_rows")
+
+
+def attn_channel_mass(qkv, lse, B, N, H, hd, scale, C, n_p, tok=None, ch=None, prescaled=False, ws=None):
+    """The attention of one block reduced to channel granularity, from qkv and the forward's lse (include/dcv.h: dcv_attn_channel_mass): with the key
+    segments S_0 = {CLS}, S_{1+c} = the n_p tokens of channel c (N = 1 + C * n_p), tok [B, H, N, 1 + C] fp32 = the mass each query puts on each
+    segment and ch [B, H, 1 + C, 1 + C] fp32 = its mean over the queries of each segment.  Either may be None, not both.  prescaled: as attn_probs.
+    ws: the caller's workspace (tests), read only for ch without tok; by default the stream's shared one."""
+    _req(qkv, torch.bfloat16, "qkv"); _req(lse, torch.float32, "lse")
+    if tok is None and ch is None:
+        raise ValueError("attn_channel_mass: tok and ch are both None")
+    if tok is not None:
+        _req(tok, torch.float32, "tok")
+    if ch is not None:
+        _req(ch, torch.float32, "ch")
+    if qkv.numel() < B * N * 3 * H * hd or lse.numel() < B * H * N or (tok is not None and tok.numel() < B * H * N * (1 + C)) or \
+            (ch is not None and ch.numel() < B * H * (1 + C) * (1 + C)):
+        raise ValueError("attn_channel_mass: qkv holds B*N*3*H*hd elements, lse B*H*N floats, tok B*H*N*(1+C), ch B*H*(1+C)*(1+C)")
+    lib = load()
+    with _timer(lambda: (f"attn_channel_mass_kernel<{'true' if prescaled else 'false'}>", f"B{B} N{N} H{H} C{C} n{n_p}", 2.0 * B * H * N * N * hd, None,
+                         2.0 * B * N * 2 * H * hd + 4.0 * B * H * N * (2 + C))):
+        if ws is None:
+            if ch is not None and tok is None:
+                ws = _workspace(_ws_size(lib.dcv_attn_channel_mass_ws_floats(B, N, H, C)), ch)
+        else:
+            _req(ws, torch.float32, "ws")
+        nws = ws.numel() if ws is not None else 0
+        if prescaled:
+            rc = lib.dcv_attn_channel_mass_ps(_p(qkv), _p(lse), _p(tok), _p(ch), B, N, H, hd, C, n_p, _p(ws), nws, _stream())
+        else:
+            rc = lib.dcv_attn_channel_mass(_p(qkv), _p(lse), _p(tok), _p(ch), B, N, H, hd, float(scale), C, n_p, _p(ws), nws, _stream())
+    _check(rc, "dcv_attn_channel_mass")
 
 
 def im2col(x, ch_idx, out, B, Ct, C, H, W, P, scale=None, shift=None):

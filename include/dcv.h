@@ -210,6 +210,20 @@ int dcv_attn_bwd_dkdv_rows_ps(const void* qkv, const void* dO, const float* lse,
  * q does not depend on Nq.  Store-bound: writes 4 B H Nq N bytes. */
 int dcv_attn_probs_rows(const void* qkv, const float* lse, float* P, int B, int N, int Nq, int H, int head_dim, float scale, void* stream);
 int dcv_attn_probs_rows_ps(const void* qkv, const float* lse, float* P, int B, int N, int Nq, int H, int head_dim, void* stream);
+/* The same probabilities reduced to CHANNEL granularity inside the kernel (ChannelVisionTransformer.get_channel_attention; no counterpart in the
+ * reference, whose users reduce get_last_selfattention's map themselves): N = 1 + C * n_p tokens (DCV_ERR_SHAPE otherwise), key segments S_0 = {0}
+ * (CLS) and S_{1+c} = the n_p tokens of channel c.  tok [B,H,N,1+C] f32: tok[b,h,q,j] = sum over k in S_j of P[b,h,q,k] (rows sum to 1);
+ * ch [B,H,1+C,1+C] f32: ch[b,h,i,j] = mean over q in S_i of tok[b,h,q,j] (row-stochastic; row 0 = tok's CLS row bit for bit).  Either output may be
+ * NULL, not both (DCV_ERR_NULL).  qkv / lse (all N rows read) as dcv_attn_fwd_rows(_ps) produced them; the _ps form takes the pre-scaled q.  P is
+ * formed as dcv_attn_probs_rows forms it and summed in fp32; no [., N, N] array is written.  No atomics: bitwise reproducible, row q of tok does
+ * not depend on the other rows, and the outputs do not depend on which of them are requested.  Two launches when ch is wanted (the query-side mean
+ * reads tok).  ws: used only for ch without tok — at least dcv_attn_channel_mass_ws_floats(B, N, H, C) = B H N (1 + C) floats (else
+ * DCV_ERR_NULL / DCV_ERR_SHAPE), contents irrelevant before and after; tok, ch, ws, lse 4-byte aligned. */
+long dcv_attn_channel_mass_ws_floats(int B, int N, int H, int C);
+int dcv_attn_channel_mass(const void* qkv, const float* lse, float* tok, float* ch, int B, int N, int H, int head_dim, float scale, int C, int n_p,
+                          float* ws, long ws_floats, void* stream);
+int dcv_attn_channel_mass_ps(const void* qkv, const float* lse, float* tok, float* ch, int B, int N, int H, int head_dim, int C, int n_p, float* ws,
+                             long ws_floats, void* stream);
 
 /* x [B,Ct,H,W] f32 (x_is_u8 == 0: normalised images, the reference's batch format) or u8 (raw pixels), ch_idx int32[C]
  * (device) -> bf16 [B*C*(H/P)*(W/P), P*P] patch rows (dichavit.py:134/210,377).  scale/shift f32[C] (nullable, indexed by
