@@ -37,6 +37,8 @@ import torch.nn.functional as F
 from . import hip
 
 LN_EPS = 1e-6  # models/dichavit.py:688,706,724,742
+_ATTN_SCALE = 64 ** -0.5  # head_dim ** -0.5: every size has 64-wide heads
+_Q_PRESCALE = _ATTN_SCALE * math.log2(math.e)  # what pre-scaled q carries (DiChaViT.attn_prescaled)
 _SIZES = {"tiny": (192, 12, 3), "small": (384, 12, 6), "base": (768, 12, 12), "distill": (384, 12, 6)}  # :676-745
 _NEW_CHANNEL_INITS = ("avg_2", "avg_2_not_in_chunk", "avg_3", "avg_3_not_in_chunk", "replicate", "zero", "random")
 
@@ -293,6 +295,13 @@ class ChannelVisionTransformer(_Holder):
         super().__setstate__(state)
         self.__dict__.setdefault("_owner", None)
 
+    def _linked_owner(self, method: str):
+        owner = self._owner() if self._owner is not None else None
+        if owner is None:
+            raise RuntimeError(f"{method} runs through the DiChaViT that owns this encoder (its parameter arena and operand "
+                               "copies); this ChannelVisionTransformer is not linked to one")
+        return owner
+
     def get_last_selfattention(self, x, extra_tokens={}, chunk="", layer_idx=-1, *, query_rows=None) -> Optional[torch.Tensor]:
         """models/dichavit.py:654-663: the softmax attention of block `layer_idx` over the tokens that block sees, fp32 [B, H, N, N] on x's
         device, detached (an inspection API: no gradient).  The tokens are prepared as forward() prepares them (chunk looked up in the
@@ -305,11 +314,7 @@ class ChannelVisionTransformer(_Holder):
         self-attention".  layer_idx >= depth or < -depth returns None, as the reference does for out-of-range values.
         query_rows=r (keyword-only extension): only the query rows [0, r) — row 0 is CLS — [B, H, r, N]; makes CLS maps possible where the
         full map does not fit (DiChaViT-B, 64 channels at 224 x 224: N = 12 545, 7.55 GB per image)."""
-        owner = self._owner() if self._owner is not None else None
-        if owner is None:
-            raise RuntimeError("get_last_selfattention runs through the DiChaViT that owns this encoder (its parameter arena and operand "
-                               "copies); this ChannelVisionTransformer is not linked to one")
-        return owner._probe_attention(x, chunk, layer_idx, query_rows)
+        return self._linked_owner("get_last_selfattention")._probe_attention(x, chunk, layer_idx, query_rows)
 
     def get_intermediate_layers(self, x, extra_tokens={}, n=1, *, chunk="", training_chunks=None, new_channel_init=None, pool=None):
         """models/dichavit.py:665-673 as it is meant: the token features of the last `n` blocks — for each of them the residual stream after that
@@ -329,11 +334,7 @@ class ChannelVisionTransformer(_Holder):
         blocks = _parse_layers(n, len(self.blocks))
         if pool not in (None, "channel"):
             raise ValueError(f"pool={pool!r}: expected None or 'channel'")
-        owner = self._owner() if self._owner is not None else None
-        if owner is None:
-            raise RuntimeError("get_intermediate_layers runs through the DiChaViT that owns this encoder (its parameter arena and operand "
-                               "copies); this ChannelVisionTransformer is not linked to one")
-        return owner._probe_layers(x, chunk, training_chunks, new_channel_init, blocks, pool)
+        return self._linked_owner("get_intermediate_layers")._probe_layers(x, chunk, training_chunks, new_channel_init, blocks, pool)
 
     def get_channel_attention(self, x, extra_tokens={}, n=1, *, chunk="", training_chunks=None, new_channel_init=None, queries="channel"):
         """Which channels does the model look at, and from where: the softmax attention of the last `n` blocks reduced to channel granularity, as a
@@ -352,11 +353,7 @@ class ChannelVisionTransformer(_Holder):
         blocks = _parse_layers(n, len(self.blocks))
         if queries not in ("channel", "token"):
             raise ValueError(f"queries={queries!r}: expected 'channel' or 'token'")
-        owner = self._owner() if self._owner is not None else None
-        if owner is None:
-            raise RuntimeError("get_channel_attention runs through the DiChaViT that owns this encoder (its parameter arena and operand "
-                               "copies); this ChannelVisionTransformer is not linked to one")
-        return owner._probe_channel_attention(x, chunk, training_chunks, new_channel_init, blocks, queries)
+        return self._linked_owner("get_channel_attention")._probe_channel_attention(x, chunk, training_chunks, new_channel_init, blocks, queries)
 
     @staticmethod
     def _init_weights(m):  # dichavit.py:509-516
@@ -468,6 +465,102 @@ class _ChannelProxyLossFn(torch.autograd.Function):
         return gg[1], gg[0], None
 
 
+# Weight-gradient products on a second stream (DiChaViT.wgrad_stream): nothing in the backward depends on them, so their
+# workgroups fill the tail of the input-gradient / attention kernels and their atomic flush overlaps the next kernel.
+# Hazards are the scratch buffers they read (dxb, dz, dqkv: the main stream waits for the last side-stream reader
+# before it overwrites one; dxb alternates between two buffers so that wait is never a stall) and the saved activations
+# (held until the streams have joined).
+# wgrad_private_scratch: every layer gets scratch of its own for the buffers the second stream reads (dz, dqkv, dxb: 0.7 GB per layer at
+# the headline shape, held until the join; the allocator recycles them step to step), so the compute stream never has to wait for
+# a reader before it overwrites one.  Those waits were always satisfied long before, but each is a barrier packet in the compute
+# queue (4 per layer) and cost ~8 us of queue time: 36.58 -> 36.23 ms per step, same bits (profiles/r03_x12_*).  On one stream too: the
+# grouped weight-gradient launch needs its operands alive.
+class _BackwardScratch:
+    """Where one backward's weight-gradient products run and the bf16 scratch they read: `self.<role>` is the current buffer of the roles
+    dz, dxb and dqkv.  side None: one stream — the current stream is never asked for, nothing is recorded or waited for."""
+
+    def __init__(self, side, dev, wgrads, private, release, **buffers):
+        self.side_all, self.main = side, torch.cuda.current_stream(dev) if side is not None else None
+        self.wgrads, self.private_all, self.release = wgrads, private, release  # wgrads False: data-only backward, no weight-gradient GEMM
+        self.side, self.private, self.dxb_alt = None, False, None  # side, private: per block (begin_block)
+        self.readers, self.held = {}, []  # id(buffer) -> the event after its last side-stream reader; what must outlive the side stream's work
+        self.__dict__.update(buffers)
+
+    def begin_block(self, tail):  # the CLS-only last block keeps its (tiny) products on the main stream, in rows of the shared buffers
+        self.side, self.private = (None, False) if tail else (self.side_all, self.private_all)
+        self.plan, self.group = (), []  # _group_ok's launch plan for this block's weight gradients, and those collected for it
+
+    def fresh(self, role):
+        """A buffer of this role that may be overwritten now; it becomes self.<role>."""
+        buf = getattr(self, role)
+        if self.private:
+            self.held.append(buf)
+            buf = torch.empty_like(buf)
+        elif self.side is not None:
+            if role == "dxb":  # a weight gradient may still be reading the old one
+                if self.dxb_alt is None or self.dxb_alt.shape != buf.shape:
+                    self.dxb_alt = torch.empty_like(buf)
+                buf, self.dxb_alt = self.dxb_alt, buf
+            ev = self.readers.pop(id(buf), None)
+            if ev is not None:
+                self.main.wait_event(ev)
+        setattr(self, role, buf)
+        return buf
+
+    def on_side(self):
+        """Context for work behind everything queued on the main stream so far, on this block's side stream when there is one."""
+        if self.side is None:
+            return contextlib.nullcontext()
+        ev = torch.cuda.Event()
+        ev.record(self.main)
+        self.side.wait_event(ev)
+        return torch.cuda.stream(self.side)
+
+    def wgrad(self, Y, X, gw, gb):
+        """A weight-gradient product (Y: the scratch buffer it reads): launched now, or collected for the block's grouped launch."""
+        if self.plan:
+            self.group.append((Y, X, gw, gb))
+        elif self.wgrads:
+            with self.on_side():
+                hip.gemm_tn_acc(Y, X, gw, gb)
+                if self.side is not None:
+                    done = torch.cuda.Event()
+                    done.record(self.side)
+                    self.readers[id(Y)] = done
+
+    def launch_group(self):
+        if self.plan:
+            with self.on_side():
+                for members in self.plan:  # one launch per group of the plan
+                    hip.gemm_tn_acc_group([self.group[i] for i in members])
+
+    def end_block(self, L):  # L, the block's saved activations, is emptied: the side stream may still be reading them
+        if self.side is not None:
+            self.held.append(dict(L))
+        L.clear()
+        if self.release or self.side is None:
+            # Everything in `held` — older layers' dz / dqkv / dxb and this layer's saved activations — has had its LAST reader queued
+            # (the block's weight-gradient launches — grouped or one by one, they are all in their queue by now).  On ONE stream that
+            # is enough to hand the memory back, and it is done (peak scratch = one layer instead of depth x 0.7 GB; ADVICE r3).  With the
+            # second stream the hand-back needs record_stream (the allocator reuses the block only after that stream's queued work), and
+            # that is OFF by default (DiChaViT.wgrad_scratch_release): measured in round 4, the deferred frees make the caching allocator
+            # fall into its slow path once every few dozen steps — ONE step of ~1000 ms among 35 ms steps in 2 of 3 runs — so the buffers
+            # are held until the streams join, as in round 3 (8.4 GB of scratch per backward for DiChaViT-S at bs 64, recycled step to step).
+            for t in self.held:
+                for v in (t.values() if isinstance(t, dict) else (t,)):
+                    if self.side is not None and torch.is_tensor(v) and v.is_cuda:
+                        v.record_stream(self.side)
+            self.held.clear()
+
+    def join(self):
+        if self.side_all is not None:
+            ev = torch.cuda.Event()
+            ev.record(self.side_all)
+            self.main.wait_event(ev)
+            self.readers.clear()
+        self.held.clear()
+
+
 class DiChaViT(nn.Module):
     def __init__(self, config, **kwargs):
         super().__init__()
@@ -497,20 +590,20 @@ class DiChaViT(nn.Module):
         self._grad_arena = None
         self._grad_scratch = None
         self._dp = None  # set by diverse_channel_vit_amd.dp.DataParallel
-        # weight-gradient GEMMs on a second HIP stream (_run_backward_body)?  Default since round 4: NO.  With one grouped launch per block and the forward
+        # weight-gradient GEMMs on a second HIP stream (_BackwardScratch)?  Default since round 4: NO.  With one grouped launch per block and the forward
         # LayerNorm inside the residual GEMMs the one-stream step is 0.13-0.18 ms FASTER (35.57-35.66 against 35.67-35.79 ms, four alternating pairs on one
         # box), needs no cross-stream events and hands every layer's scratch back at once; DCV_WGRAD_STREAM=1 / model.wgrad_stream = True selects two streams.
         self.wgrad_stream = os.environ.get("DCV_WGRAD_STREAM", "0") == "1"
-        self.wgrad_private_scratch = os.environ.get("DCV_WGRAD_PRIVATE", "1") != "0"  # per-layer scratch instead of reader waits (_run_backward_body)
+        self.wgrad_private_scratch = os.environ.get("DCV_WGRAD_PRIVATE", "1") != "0"  # per-layer scratch instead of reader waits (_BackwardScratch)
         self.fused_proxy_loss = os.environ.get("DCV_FUSED_PROXY_LOSS", "1") != "0"  # the channel-embedding proxy term as one kernel (dcv_proxy_loss)
         # Pre-scaled q (round 4): the bf16 operand copy of W_q and the q part of the qkv bias are multiplied by scale * log2(e) when the copies are
         # refreshed (one rounding, as before), so the qkv GEMM delivers q' = q scale log2 e; the three attention kernels then start their score
         # accumulators at the row constants (-m, -LSE log2 e, -delta) and exp2 the accumulator directly: one vector instruction less per score in
         # vector-issue-bound loops (dcv_attn_*_ps).  DCV_ATTN_PS=0 / model.attn_prescaled = False: the plain entries.  Not with the one-pass backward.
         self.attn_prescaled = os.environ.get("DCV_ATTN_PS", "1") != "0"
-        self.fuse_ln_min_tiles = int(os.environ.get("DCV_FUSE_LN_MIN_TILES", "96"))  # 256-row tiles below which the fusion does not pay (_run_forward)
+        self.fuse_ln_min_tiles = int(os.environ.get("DCV_FUSE_LN_MIN_TILES", "96"))  # 256-row tiles below which the fusion does not pay (_tokenise)
         self.fuse_ln_fwd = os.environ.get("DCV_FUSE_LN", "1") != "0"  # forward LayerNorm inside the residual GEMMs' epilogue (dcv_gemm_nt_resid_ln; D = 384)
-        self.wgrad_scratch_release = os.environ.get("DCV_WGRAD_RELEASE", "0") == "1"  # two streams: record_stream hand-back per layer (allocator stalls: see _run_backward_body)
+        self.wgrad_scratch_release = os.environ.get("DCV_WGRAD_RELEASE", "0") == "1"  # two streams: record_stream hand-back per layer (allocator stalls: see _BackwardScratch.end_block)
         self.wgrad_group = os.environ.get("DCV_WGRAD_GROUP", "1") != "0"  # a block's four weight gradients in one launch (needs the private scratch)
         self._group_cache = {}
         self._stats_w = {}
@@ -615,20 +708,19 @@ class DiChaViT(nn.Module):
     def _refresh_operand_copies(self, stochastic: bool = False, prescale_q: bool = False):
         """prescale_q: W_q rows of the straight copy and the q part of the bias copy times scale * log2(e) (attn_prescaled); the transposed copy
         stays unscaled (the input-gradient GEMM multiplies by it the gradient with respect to the unscaled q)."""
-        qc = (64 ** -0.5) * math.log2(math.e)
         if stochastic:
             if self._sr_seed is None or self._sr_seed.device != self._arena.device:
                 self._sr_seed = torch.full((1,), int(_cfg_get(self.cfg, "weight_rounding_seed", 1)), dtype=torch.int32, device=self._arena.device)
             hip.cast_bf16_sr(self._arena, self._bf16, self._enc_size, self._sr_seed)
             hip.cast_transpose_bf16_sr(self._arena, self._bf16_t, self._tdesc, self._tdesc_n, self._tdesc_tiles, self._sr_seed)
             if prescale_q:
-                hip.cast_scaled_ranges(self._arena, self._bf16, self._qbias, self._qdesc, self._qdesc.shape[0], 64, qc, self._sr_seed)
+                hip.cast_scaled_ranges(self._arena, self._bf16, self._qbias, self._qdesc, self._qdesc.shape[0], 64, _Q_PRESCALE, self._sr_seed)
             self._sr_seed.add_(1)  # a device-side bump: replays of a captured step draw fresh bits too
             return
         hip.cast_bf16(self._arena, self._bf16, self._enc_size)
         hip.cast_transpose_bf16(self._arena, self._bf16_t, self._tdesc, self._tdesc_n, self._tdesc_tiles)
         if prescale_q:
-            hip.cast_scaled_ranges(self._arena, self._bf16, self._qbias, self._qdesc, self._qdesc.shape[0], 64, qc)
+            hip.cast_scaled_ranges(self._arena, self._bf16, self._qbias, self._qdesc, self._qdesc.shape[0], 64, _Q_PRESCALE)
 
     def _new_grad_arena(self):
         """A zeroed flat gradient buffer for the encoder parameters.  The arena is reused when no parameter's .grad still aliases it
@@ -895,50 +987,21 @@ class DiChaViT(nn.Module):
             out.append(tuple(pair))
         return out
 
-    def _run_forward(self, x, ch_idx_dev, C, E, pos_tab, want_ortho, save, keep=None, st_scale=None, st_shift=None, tok=None, probe=None,
-                     capture=None, frozen_k=None, chan_attn=None):
-        """frozen_k=k (with save): blocks < k and the tokeniser keep nothing for the backward (they run as with save=False, on the same
-        kernels); st["layers"] still has one entry per block — the backward indexes it by block number — which for blocks < k holds the
-        DropPath factors only.
-        probe=(layer, rows): get_last_selfattention — run blocks < layer as the forward does, stop at block `layer` after its norm1 and qkv
-        GEMM and return its attention probabilities [B, H, rows, N] (fp32) instead of the state.  Needs save=False and want_ortho=False.  The
-        model's operand copies (_bf16, _bf16_t, _qbias) and _sr_seed are left alone — a training forward's backward may still read them — and
-        round-to-nearest straight copies are cast into scratch instead.
-        capture=(blocks, pool): get_intermediate_layers — the same discipline; every block runs on all rows (no CLS-only tail), the final norm of
-        the stream after each block of `blocks` (ascending) is launched right after that block — with save=False the stream is updated in place,
-        so the capture is stream-ordered before the next block overwrites it — and the list of captures is returned after the last of them
-        instead of the state.  pool=None: [B, N, D] (dcv_ln_fwd, fp32 output); pool="channel": [B, 1 + C, D] (dcv_ln_pool_channels).
-        chan_attn=(blocks, queries): get_channel_attention — the same discipline again (scratch operand copies, every block on all rows); a block of
-        `blocks` (ascending) runs its ordinary attention and then dcv_attn_channel_mass on its qkv and LSE — queries="channel": [B, H, 1 + C, 1 + C],
-        "token": [B, H, N, 1 + C], the key segments by (C, n) — and the list is returned right after the last of them: the rest of that block and
-        every later block never run.  Needs keep=None (whole segments)."""
-        fe = self.feature_extractor
-        D, H = self.dim, fe.num_heads
-        P = fe.patch_size
+    def _tokenise(self, x, ch_idx_dev, C, E, pos_tab, want_ortho, keep, st_scale, st_shift, tok, wbuf=None, qbias=None):
+        """The tokeniser: im2col -> MFMA GEMM with (+bias +channel_embed[c] +pos[i]) epilogue, CLS fill, ortho statistics, token gather.
+        wbuf / qbias: straight bf16 operand copies and q bias other than the model's own (_inspection_tokenise).  Returns (f, the residual
+        stream [M, D], the ortho statistics [B, 2], what the tokeniser's backward needs); f is what the blocks of this forward share: the
+        shapes the encoder sees, `wb(p)` (the bf16 operand copy of p), the q bias, pre-scaled q or not, DropPath factors, fused LayerNorm or not."""
+        fe, dev = self.feature_extractor, x.device
+        pe, D, P = fe.patch_embed, self.dim, fe.patch_size
         B, Ct, Hi, Wi = x.shape
         n = (Hi // P) * (Wi // P)
         T, N = C * n, C * n + 1
-        M = B * N
-        dev = x.device
         bf, f32 = torch.bfloat16, torch.float32
-        ps = bool(self.attn_prescaled)  # pre-scaled q for this forward AND its backward (kept in the saved state)
-        if probe is None and capture is None and chan_attn is None:
-            self._refresh_operand_copies(stochastic=bool(save) and self.training and self.stochastic_weight_rounding, prescale_q=ps)
-            wbuf, qbias = None, self._qbias
-        else:
-            assert not save and not want_ortho
-            wbuf, qbias = torch.empty_like(self._bf16), torch.empty_like(self._qbias)
-            hip.cast_bf16(self._arena, wbuf, self._enc_size)
-            if ps:
-                hip.cast_scaled_ranges(self._arena, wbuf, qbias, self._qdesc, self._qdesc.shape[0], 64, (64 ** -0.5) * math.log2(math.e))
         wb = lambda p: self._bf(p, buf=wbuf)  # noqa: E731
-        pe = fe.patch_embed
         # (channels, positions) structure of the embedding rows the tokeniser epilogue adds: (C, n) normally, (1, C*n) when the
         # positional table is per token (the reference's early-out, _pos_table)
         Ctok, ntok = tok if tok is not None else (C, n)
-        fk = frozen_k if save else None
-        st = dict(B=B, C=C, n=n, N=N, M=M, save=save, tok=(Ctok, ntok), ps=ps, frozen_k=fk)
-        # --- tokeniser: im2col -> MFMA GEMM with (+bias +channel_embed[c] +pos[i]) epilogue ---
         Xp = torch.empty(B * T, P * P, dtype=bf, device=dev)
         hip.im2col(x, ch_idx_dev, Xp, B, Ct, C, Hi, Wi, P, scale=st_scale, shift=st_shift)
         xs = torch.empty(B, N, D, dtype=f32, device=dev)
@@ -948,139 +1011,133 @@ class DiChaViT(nn.Module):
                     ldo=D, ldo2=D, ldaux=D)
         hip.fill_cls(xs, fe.cls_token, pc, B, N * D, D)
         stats = torch.zeros(B, 2, dtype=f32, device=dev)
+        kept = dict(Xp=Xp)
         if want_ortho:
-            S = torch.empty(B, C, D, dtype=f32, device=dev)
-            selfsq = torch.empty(B, C, dtype=f32, device=dev)
-            tot = torch.empty(B, D, dtype=f32, device=dev)
-            inv = torch.empty(B, T, dtype=f32, device=dev)
+            S, selfsq, tot, inv = (torch.empty(B, *sh, dtype=f32, device=dev) for sh in ((C, D), (C,), (D,), (T,)))
             hip.ortho_fwd(Y, S, selfsq, tot, inv, stats, B, C, n, D)
-            if save and fk is None:
-                st.update(Y=Y, S=S, tot=tot, inv=inv)
-        if save and fk is None:
-            st["Xp"] = Xp
+            kept.update(Y=Y, S=S, tot=tot, inv=inv)
         if keep is not None:  # dropout_tokens_hcs: the encoder sees only the kept token rows (CLS first)
-            keep_dev = self._index_tensor(keep, torch.int32, dev, cache=False)
-            Nk = len(keep)
+            keep_dev, Nk = self._index_tensor(keep, torch.int32, dev, cache=False), len(keep)
             xk = torch.empty(B, Nk, D, dtype=f32, device=dev)
             hip.gather_tokens(xs, keep_dev, xk, B, N, Nk, D)
-            st.update(keep_dev=keep_dev, N_full=N)
+            kept.update(keep_dev=keep_dev, N_full=N)
             xs, N = xk, Nk
-            M = B * N
-            st.update(N=N, M=M)
-        # --- encoder blocks ---
-        scale = 64 ** -0.5
-        layers, captured = [], []
-        xcur = xs.view(M, D)
-        final_stride = N * D
-        drop = self._drop_path_scales(B, dev)
+        M = B * N
         # LayerNorm from the residual GEMM's accumulators (judge row N1, round 4): needs a tile that spans whole rows (D = 384, the 256 x 384 kernel)
         # ... and enough rows to fill the chip with 256-row tiles: below ~96 tiles (M < 24.5 k rows: the CHAMMI sub-batches, 12-22 k rows) the residual GEMM
         # on the narrow kernel's three-times-as-many tiles plus a separate ln_fwd is faster (measured: CHAMMI step 29.5 vs 30.6 ms, bs 16 equal, bs 32
         # 19.1 -> 18.6 ms, bs 64 36.45 -> 35.85 ms)
         fuse_ln = bool(self.fuse_ln_fwd) and D == 384 and (M + 255) // 256 >= self.fuse_ln_min_tiles
+        f = types.SimpleNamespace(B=B, C=C, n=n, N=N, M=M, D=D, H=fe.num_heads, dev=dev, tok=(Ctok, ntok), wb=wb, ps=bool(self.attn_prescaled),
+                                  qbias=self._qbias if qbias is None else qbias, drop=self._drop_path_scales(B, dev), fuse_ln=fuse_ln)
+        return f, xs.view(M, D), stats, kept
+
+    def _block_attention(self, f, bi, xcur, pre_ln, nq=None):
+        """First half of encoder block bi: norm1 — or `pre_ln`, its (output, mean, rstd) as they came out of the previous block's fc2 + residual
+        epilogue —, the qkv GEMM and the attention of every query row, or of rows [0, nq) only (keys and values still come from all tokens).
+        Returns what it made, under the names the backward reads them by."""
+        blk = self.feature_extractor.blocks[bi]
+        B, N, M, D, H, dev = f.B, f.N, f.M, f.D, f.H, f.dev
+        bf, f32 = torch.bfloat16, torch.float32
+        if pre_ln is not None:
+            u1, mean1, rstd1 = pre_ln
+        else:
+            u1 = torch.empty(M, D, dtype=bf, device=dev)
+            mean1, rstd1 = torch.empty(M, dtype=f32, device=dev), torch.empty(M, dtype=f32, device=dev)
+            hip.ln_fwd(xcur, blk.norm1.weight, blk.norm1.bias, u1, mean1, rstd1, M, D, LN_EPS)
+        qkv = torch.empty(M, 3 * D, dtype=bf, device=dev)
+        hip.gemm_nt(u1, f.wb(blk.attn.qkv.weight), hip.EPI_BIAS_BF16, qkv, bias=f.qbias[bi] if f.ps else blk.attn.qkv.bias)
+        o = torch.empty(M, D, dtype=bf, device=dev)
+        lse = torch.empty(B, H, N, dtype=f32, device=dev)
+        hip.attn_fwd(qkv, o, lse, B, N, H, D // H, _ATTN_SCALE, prescaled=f.ps, **({} if nq is None else dict(nq=nq)))
+        return dict(u1=u1, mean1=mean1, rstd1=rstd1, qkv=qkv, o=o, lse=lse)
+
+    def _block_residuals(self, f, bi, xcur, a, sv=False, tail=False):
+        """Second half of encoder block bi, after the attention `a` (_block_attention): attn.proj + residual, norm2, MLP, fc2 + residual.  sv: the
+        activations are kept for the backward (the stream goes to fresh buffers, otherwise it is updated in place).  tail: the CLS rows only.
+        Returns (the stream after the block, the next block's norm1 if it came out of the fc2 epilogue else None, the block's saved state)."""
+        fe = self.feature_extractor
+        blk, nxt = fe.blocks[bi], fe.blocks[bi + 1] if bi + 1 < len(fe.blocks) else None
+        B, N, M, D, dev = f.B, f.N, f.M, f.D, f.dev
+        bf, f32 = torch.bfloat16, torch.float32
+        o, wb = a["o"], f.wb
+        dsc = f.drop[bi] if f.drop is not None else None  # (attention branch, MLP branch) DropPath factors [B] or None
+        if tail:
+            # The encoder's output is read at the CLS row only (norm(x)[:, 0], dichavit.py:651-652), so in the LAST block
+            # every token-wise op after the attention needs the CLS rows alone, and the attention only the CLS query
+            # (keys and values still come from all tokens).  Same values and gradients as the reference, which computes
+            # — and then discards — the other rows.
+            o_c = o.view(B, N, D)[:, 0].contiguous()
+            x_c = xcur.view(B, N, D)[:, 0].contiguous()
+            xmid = torch.empty(B, D, dtype=f32, device=dev)
+            hip.gemm_nt(o_c, wb(blk.attn.proj.weight), hip.EPI_BIAS_RESID_F32, xmid, bias=blk.attn.proj.bias, aux=x_c,
+                        **(dict(aux2=dsc[0], T=1) if dsc else {}))
+            R = B  # rows the rest of this block works on
+        else:
+            o_c = None
+            xmid = torch.empty(M, D, dtype=f32, device=dev) if sv else xcur
+            R = M
+        u2 = torch.empty(R, D, dtype=bf, device=dev)
+        mean2, rstd2 = torch.empty(R, dtype=f32, device=dev), torch.empty(R, dtype=f32, device=dev)
+        if tail:
+            hip.ln_fwd(xmid, blk.norm2.weight, blk.norm2.bias, u2, mean2, rstd2, R, D, LN_EPS)
+        elif f.fuse_ln:
+            # attn.proj + residual AND norm2 from the accumulators of one launch (dcv_gemm_nt_resid_ln): no re-read of xmid
+            hip.gemm_nt_resid_ln(o, wb(blk.attn.proj.weight), blk.attn.proj.bias, xcur, xmid, blk.norm2.weight, blk.norm2.bias,
+                                 LN_EPS, u2, mean2, rstd2, **(dict(branch_scale=dsc[0], T=N) if dsc else {}))
+        else:
+            hip.gemm_nt(o, wb(blk.attn.proj.weight), hip.EPI_BIAS_RESID_F32, xmid, bias=blk.attn.proj.bias, aux=xcur,
+                        **(dict(aux2=dsc[0], T=N) if dsc else {}))
+            hip.ln_fwd(xmid, blk.norm2.weight, blk.norm2.bias, u2, mean2, rstd2, R, D, LN_EPS)
+        z = torch.empty(R, 4 * D, dtype=bf, device=dev)  # GELU'(pre-activation), saved for the backward
+        hact = torch.empty(R, 4 * D, dtype=bf, device=dev)
+        hip.gemm_nt(u2, wb(blk.mlp.fc1.weight), hip.EPI_BIAS_GELU_BF16, z, bias=blk.mlp.fc1.bias, out2=hact)
+        xout = torch.empty(R, D, dtype=f32, device=dev) if (sv or tail) else xmid
         pre_ln = None
-        for bi, blk in enumerate(fe.blocks):
-            L = {}
+        if f.fuse_ln and not tail and nxt is not None:
+            # mlp.fc2 + residual AND the NEXT block's norm1 (its full rows are needed even when that block is the CLS-only tail: keys and values)
+            un = torch.empty(M, D, dtype=bf, device=dev)
+            mn, rn = torch.empty(M, dtype=f32, device=dev), torch.empty(M, dtype=f32, device=dev)
+            hip.gemm_nt_resid_ln(hact, wb(blk.mlp.fc2.weight), blk.mlp.fc2.bias, xmid, xout, nxt.norm1.weight, nxt.norm1.bias, LN_EPS,
+                                 un, mn, rn, **(dict(branch_scale=dsc[1], T=R // B) if dsc else {}))
+            pre_ln = (un, mn, rn)
+        else:
+            hip.gemm_nt(hact, wb(blk.mlp.fc2.weight), hip.EPI_BIAS_RESID_F32, xout, bias=blk.mlp.fc2.bias, aux=xmid,
+                        **(dict(aux2=dsc[1], T=R // B) if dsc else {}))
+        kept = dict(x_in=xcur, **a, x_mid=xmid, u2=u2, mean2=mean2, rstd2=rstd2, z=z, h=hact, tail=tail, o_c=o_c) if sv else {}
+        return xout, pre_ln, dict(drop=dsc, **kept)  # the DropPath factors: all that the block above reads from a block that is not kept
+
+    def _block_forward(self, f, bi, xcur, pre_ln, sv=False, tail=False):
+        """Encoder block bi on every row, or as the CLS-only tail: the CLS query and, after the attention, the CLS rows alone."""
+        return self._block_residuals(f, bi, xcur, self._block_attention(f, bi, xcur, pre_ln, nq=1 if tail else None), sv, tail)
+
+    def _final_norm(self, f, xcur, row_stride):
+        """The final LayerNorm on the CLS rows only (dichavit.py:651-652): (feature [B, D], mean, rstd)."""
+        fe = self.feature_extractor
+        feat, meanf, rstdf = (torch.empty(f.B, *sh, dtype=torch.float32, device=f.dev) for sh in ((f.D,), (), ()))
+        hip.ln_fwd(xcur, fe.norm.weight, fe.norm.bias, feat, meanf, rstdf, f.B, f.D, LN_EPS, x_row_stride=row_stride)
+        return feat, meanf, rstdf
+
+    def _run_forward(self, x, ch_idx_dev, C, E, pos_tab, want_ortho, save, keep=None, st_scale=None, st_shift=None, tok=None, frozen_k=None):
+        """The training / eval forward: operand copies, tokeniser, blocks, final norm.  Returns the state: feat, stats and, with save, what the
+        backward reads.  frozen_k=k (with save): blocks < k and the tokeniser keep nothing for the backward (they run as with save=False, on
+        the same kernels); st["layers"] still has one entry per block — the backward indexes it by block number — which for blocks < k holds
+        the DropPath factors only."""
+        depth = len(self.feature_extractor.blocks)
+        self._refresh_operand_copies(stochastic=bool(save) and self.training and self.stochastic_weight_rounding, prescale_q=bool(self.attn_prescaled))
+        f, xcur, stats, kept = self._tokenise(x, ch_idx_dev, C, E, pos_tab, want_ortho, keep, st_scale, st_shift, tok)
+        fk = frozen_k if save else None
+        st = dict(B=f.B, C=C, n=f.n, N=f.N, M=f.M, save=save, tok=f.tok, ps=f.ps, frozen_k=fk)
+        if save and fk is None:
+            st.update(kept)
+        layers, pre_ln = [], None
+        for bi in range(depth):
             sv = save and (fk is None or bi >= fk)  # this block's activations are kept for the backward
-            tail = self.cls_only_tail and bi == len(fe.blocks) - 1 and capture is None and chan_attn is None  # a captured last block runs on all rows
-            dsc = drop[bi] if drop is not None else None  # (attention branch, MLP branch) factors [B] or None
-            if pre_ln is not None:  # norm1 of this block came out of the previous block's fc2 + residual epilogue
-                u1, mean1, rstd1 = pre_ln
-                pre_ln = None
-            else:
-                u1 = torch.empty(M, D, dtype=bf, device=dev)
-                mean1, rstd1 = torch.empty(M, dtype=f32, device=dev), torch.empty(M, dtype=f32, device=dev)
-                hip.ln_fwd(xcur, blk.norm1.weight, blk.norm1.bias, u1, mean1, rstd1, M, D, LN_EPS)
-            qkv = torch.empty(M, 3 * D, dtype=bf, device=dev)
-            hip.gemm_nt(u1, wb(blk.attn.qkv.weight), hip.EPI_BIAS_BF16, qkv, bias=qbias[bi] if ps else blk.attn.qkv.bias)
-            o = torch.empty(M, D, dtype=bf, device=dev)
-            lse = torch.empty(B, H, N, dtype=f32, device=dev)
-            if probe is not None and bi == probe[0]:
-                # the probed block: LSE of its query rows from the forward kernel, then the probabilities written once; no later block runs
-                rows = probe[1]
-                hip.attn_fwd(qkv, o, lse, B, N, H, D // H, scale, nq=rows, prescaled=ps)
-                probs = torch.empty(B, H, rows, N, dtype=f32, device=dev)
-                hip.attn_probs(qkv, lse, probs, B, N, H, D // H, scale, nq=rows, prescaled=ps)
-                return probs
-            if tail:
-                # The encoder's output is read at the CLS row only (norm(x)[:, 0], dichavit.py:651-652), so in the LAST block
-                # every token-wise op after the attention needs the CLS rows alone, and the attention only the CLS query
-                # (keys and values still come from all tokens).  Same values and gradients as the reference, which computes
-                # — and then discards — the other rows.
-                hip.attn_fwd(qkv, o, lse, B, N, H, D // H, scale, nq=1, prescaled=ps)
-                o_c = o.view(B, N, D)[:, 0].contiguous()
-                x_c = xcur.view(B, N, D)[:, 0].contiguous()
-                xmid = torch.empty(B, D, dtype=f32, device=dev)
-                hip.gemm_nt(o_c, wb(blk.attn.proj.weight), hip.EPI_BIAS_RESID_F32, xmid, bias=blk.attn.proj.bias, aux=x_c,
-                            **(dict(aux2=dsc[0], T=1) if dsc else {}))
-                R = B  # rows the rest of this block works on
-            else:
-                hip.attn_fwd(qkv, o, lse, B, N, H, D // H, scale, prescaled=ps)
-                if chan_attn is not None and bi in chan_attn[0]:
-                    cap = torch.empty((B, H, N, 1 + C) if chan_attn[1] == "token" else (B, H, 1 + C, 1 + C), dtype=f32, device=dev)
-                    hip.attn_channel_mass(qkv, lse, B, N, H, D // H, scale, C, n, prescaled=ps,
-                                          **{"tok" if chan_attn[1] == "token" else "ch": cap})
-                    captured.append(cap)
-                    if bi == chan_attn[0][-1]:
-                        return captured
-                o_c = None
-                xmid = torch.empty(M, D, dtype=f32, device=dev) if sv else xcur
-                R = M
-                if fuse_ln:
-                    # attn.proj + residual AND norm2 from the accumulators of one launch (dcv_gemm_nt_resid_ln): no re-read of xmid
-                    u2 = torch.empty(R, D, dtype=bf, device=dev)
-                    mean2, rstd2 = torch.empty(R, dtype=f32, device=dev), torch.empty(R, dtype=f32, device=dev)
-                    hip.gemm_nt_resid_ln(o, wb(blk.attn.proj.weight), blk.attn.proj.bias, xcur, xmid, blk.norm2.weight, blk.norm2.bias,
-                                         LN_EPS, u2, mean2, rstd2, **(dict(branch_scale=dsc[0], T=N) if dsc else {}))
-                else:
-                    hip.gemm_nt(o, wb(blk.attn.proj.weight), hip.EPI_BIAS_RESID_F32, xmid, bias=blk.attn.proj.bias, aux=xcur,
-                                **(dict(aux2=dsc[0], T=N) if dsc else {}))
-            if tail or not fuse_ln:
-                u2 = torch.empty(R, D, dtype=bf, device=dev)
-                mean2, rstd2 = torch.empty(R, dtype=f32, device=dev), torch.empty(R, dtype=f32, device=dev)
-                hip.ln_fwd(xmid, blk.norm2.weight, blk.norm2.bias, u2, mean2, rstd2, R, D, LN_EPS)
-            z = torch.empty(R, 4 * D, dtype=bf, device=dev)  # GELU'(pre-activation), saved for the backward
-            hact = torch.empty(R, 4 * D, dtype=bf, device=dev)
-            hip.gemm_nt(u2, wb(blk.mlp.fc1.weight), hip.EPI_BIAS_GELU_BF16, z, bias=blk.mlp.fc1.bias, out2=hact)
-            xout = torch.empty(R, D, dtype=f32, device=dev) if (sv or tail) else xmid
-            # a capture that ends at this block keeps this launch although block bi + 1 never runs: the stream of block bi must come from the
-            # same kernel whether or not later blocks are requested (n=4 equals four single-index calls bit for bit), at the cost of one unused
-            # norm1 output in the epilogue
-            nxt = fe.blocks[bi + 1] if bi + 1 < len(fe.blocks) else None
-            if fuse_ln and not tail and nxt is not None:
-                # mlp.fc2 + residual AND the NEXT block's norm1 (its full rows are needed even when that block is the CLS-only tail: keys and values)
-                un = torch.empty(M, D, dtype=bf, device=dev)
-                mn, rn = torch.empty(M, dtype=f32, device=dev), torch.empty(M, dtype=f32, device=dev)
-                hip.gemm_nt_resid_ln(hact, wb(blk.mlp.fc2.weight), blk.mlp.fc2.bias, xmid, xout, nxt.norm1.weight, nxt.norm1.bias, LN_EPS,
-                                     un, mn, rn, **(dict(branch_scale=dsc[1], T=R // B) if dsc else {}))
-                pre_ln = (un, mn, rn)
-            else:
-                hip.gemm_nt(hact, wb(blk.mlp.fc2.weight), hip.EPI_BIAS_RESID_F32, xout, bias=blk.mlp.fc2.bias, aux=xmid,
-                            **(dict(aux2=dsc[1], T=R // B) if dsc else {}))
-            if save and not sv:
-                layers.append(dict(drop=dsc))  # a frozen block: only what the block above reads from it
-            if sv:
-                L.update(drop=dsc)
-                L.update(x_in=xcur, u1=u1, mean1=mean1, rstd1=rstd1, qkv=qkv, o=o, lse=lse, x_mid=xmid, u2=u2, mean2=mean2,
-                         rstd2=rstd2, z=z, h=hact, tail=tail, o_c=o_c)
-                layers.append(L)
-            xcur = xout
-            if capture is not None and bi in capture[0]:
-                if capture[1] == "channel":
-                    cap = torch.empty(B, 1 + C, D, dtype=f32, device=dev)
-                    hip.ln_pool_channels(xcur, fe.norm.weight, fe.norm.bias, cap, B, C, n, D, LN_EPS)
-                else:
-                    cap = torch.empty(B, N, D, dtype=f32, device=dev)
-                    hip.ln_fwd(xcur, fe.norm.weight, fe.norm.bias, cap, None, None, M, D, LN_EPS)
-                captured.append(cap)
-                if bi == capture[0][-1]:
-                    return captured
-            if tail:
-                final_stride = D  # the last block handed over compact CLS rows
-        # --- final LayerNorm on the CLS rows only (dichavit.py:651-652) ---
-        feat = torch.empty(B, D, dtype=f32, device=dev)
-        meanf, rstdf = torch.empty(B, dtype=f32, device=dev), torch.empty(B, dtype=f32, device=dev)
-        hip.ln_fwd(xcur, fe.norm.weight, fe.norm.bias, feat, meanf, rstdf, B, D, LN_EPS, x_row_stride=final_stride)
+            tail = self.cls_only_tail and bi == depth - 1  # last block on the CLS rows only: it hands over compact CLS rows
+            xcur, pre_ln, L = self._block_forward(f, bi, xcur, pre_ln, sv, tail)
+            layers.append(L)
+        final_stride = f.D if tail else f.N * f.D
+        feat, meanf, rstdf = self._final_norm(f, xcur, final_stride)
         st.update(feat=feat, stats=stats)
         if save:
             st.update(layers=layers, x_final=xcur, final_stride=final_stride, meanf=meanf, rstdf=rstdf, want_ortho=want_ortho)
@@ -1127,24 +1184,21 @@ class DiChaViT(nn.Module):
         return out
 
     def _run_backward_body(self, st, dfeat, dstats, ga, g, dp, nt_kw):
-        fe = self.feature_extractor
+        """Final norm, blocks in reverse, join of the streams, tokeniser.  ga None: data-only backward (no weight-gradient GEMM)."""
+        fe, dev = self.feature_extractor, dfeat.device
         D, H = self.dim, fe.num_heads
-        B, C, n, N, M = st["B"], st["C"], st["n"], st["N"], st["M"]
-        T = C * n
-        dev = dfeat.device
+        B, N, M = st["B"], st["N"], st["M"]
         bf, f32 = torch.bfloat16, torch.float32
         # --- final LayerNorm (CLS rows) ---
-        wgrads = ga is not None  # False: data-only backward (no weight-gradient GEMM)
-        fs = st["final_stride"]
-        compact = fs == D  # the last block ran on the CLS rows only: its gradients are [B, D] until its attention
-        dx = torch.zeros(B if compact else M, D, dtype=f32, device=dev)
+        fs = st["final_stride"]  # D: the last block ran on the CLS rows only, its gradients are [B, D] until its attention
+        dx = torch.zeros(B if fs == D else M, D, dtype=f32, device=dev)
         hip.ln_bwd(dfeat, st["x_final"], st["meanf"], st["rstdf"], fe.norm.weight, None, dx, None, g(fe.norm.weight), g(fe.norm.bias),
                    B, D, x_row_stride=fs, dx_row_stride=fs)
         dxb = torch.empty_like(dx, dtype=bf)
         # DropPath (vit.py:37-56): the gradient that enters a residual branch is the stream's gradient times that branch's per-sample
         # factor.  The bf16 copy `dxb` is what the branch's backward reads (input gradient and weight gradient), so the factor goes into
-        # the copy — here for the last block's MLP branch, below inside every LayerNorm backward for the branch under it; the fp32
-        # stream `dx` itself stays unscaled.
+        # the copy — here for the last block's MLP branch, in _block_backward inside every LayerNorm backward for the branch under it; the
+        # fp32 stream `dx` itself stays unscaled.
         top = st["layers"][-1].get("drop")
         if top is not None:
             rows = dx.shape[0] // B
@@ -1153,192 +1207,95 @@ class DiChaViT(nn.Module):
             hip.cast_bf16(dx, dxb, dx.numel())
         if dp is not None:
             dp.grad_ready(ga, *self._range_of([fe.norm.weight, fe.norm.bias]))
-        scale = 64 ** -0.5
-        ps = bool(st.get("ps"))  # the forward of this pass ran with pre-scaled q: qkv holds q', the backward entries must match
         fk = st.get("frozen_k")  # frozen prefix: the loop stops above block fk and the tokeniser's backward is not launched
         k0 = 0 if fk is None else fk
         Ms = M if k0 < len(fe.blocks) else 0  # fk == depth: only the final LayerNorm's backward (above) runs
-        dz = torch.empty(Ms, 4 * D, dtype=bf, device=dev)
-        du = torch.empty(Ms, D, dtype=bf, device=dev)
-        dO = torch.empty(Ms, D, dtype=bf, device=dev)
-        dqkv = torch.empty(Ms, 3 * D, dtype=bf, device=dev)
-        delta = torch.empty(2, B, H, N if Ms else 0, dtype=f32, device=dev)  # attention backward workspace: -delta, lse*log2e
-        # Weight-gradient products on a second stream (self.wgrad_stream): nothing in the backward depends on them, so their
-        # workgroups fill the tail of the input-gradient / attention kernels and their atomic flush overlaps the next kernel.
-        # Hazards are the scratch buffers they read (dxb, dz, dqkv: the main stream waits for the last side-stream reader
-        # before it overwrites one; dxb alternates between two buffers so that wait is never a stall) and the saved activations
-        # (held until the streams have joined).
-        main = torch.cuda.current_stream(dev)
-        side_all = self._side_stream(dev) if self.wgrad_stream else None
-        side = None  # per layer: the CLS-only last block keeps its (tiny) products on the main stream
-        readers, held = {}, []
-
-        def wgrad(Y, X, gw, gb, key):
-            if not wgrads:
-                return
-            if side is None:
-                hip.gemm_tn_acc(Y, X, gw, gb)
-                return
-            ev = torch.cuda.Event()
-            ev.record(main)
-            side.wait_event(ev)
-            with torch.cuda.stream(side):
-                hip.gemm_tn_acc(Y, X, gw, gb)
-                done = torch.cuda.Event()
-                done.record(side)
-            readers[key] = done
-
-        # wgrad_group (with private scratch): a block's four weight-gradient products go out as ONE launch (dcv_gemm_tn_group) once the last of
-        # their operands (dqkv) exists: the tiles of all four fill the CUs, so each is split 7 ways over the token rows instead of 21-85 ways
-        grp = []
-
-        def wgrad_or_collect(Y, X, gw, gb, key, grouped):
-            if not wgrads:
-                return
-            if grouped:
-                grp.append((Y, X, gw, gb))
-            else:
-                wgrad(Y, X, gw, gb, key)
-
-        def launch_group(plan):
-            items = list(grp)
-            grp.clear()
-            if side is not None:
-                ev = torch.cuda.Event()
-                ev.record(main)
-                side.wait_event(ev)
-            with (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
-                for members in plan:  # one launch per group of the plan (_group_ok)
-                    hip.gemm_tn_acc_group([items[i] for i in members])
-
-        def before_write(key):
-            ev = readers.pop(key, None)
-            if ev is not None:
-                main.wait_event(ev)
-
-        def join():
-            if side_all is not None:
-                ev = torch.cuda.Event()
-                ev.record(side_all)
-                main.wait_event(ev)
-                readers.clear()
-
-        dxb_alt = None
-        # wgrad_private_scratch: every layer gets scratch of its own for the buffers the second stream reads (dz, dqkv, dxb: 0.7 GB per layer at
-        # the headline shape, held until the join below; the allocator recycles them step to step), so the compute stream never has to wait for
-        # a reader before it overwrites one.  Those waits were always satisfied long before, but each is a barrier packet in the compute
-        # queue (4 per layer) and cost ~8 us of queue time: 36.58 -> 36.23 ms per step, same bits (profiles/r03_x12_*).
-        private = bool(self.wgrad_private_scratch)  # on one stream too: the grouped weight-gradient launch below needs its operands alive
+        sc = _BackwardScratch(self._side_stream(dev) if self.wgrad_stream else None, dev, ga is not None, bool(self.wgrad_private_scratch),
+                              bool(self.wgrad_scratch_release), dxb=dxb, dz=torch.empty(Ms, 4 * D, dtype=bf, device=dev),
+                              dqkv=torch.empty(Ms, 3 * D, dtype=bf, device=dev))
+        # what the blocks' backwards share; ps: the forward of this pass ran with pre-scaled q: qkv holds q', the backward entries must match
+        b = types.SimpleNamespace(B=B, N=N, M=M, g=g, nt_kw=nt_kw, ps=bool(st.get("ps")), sc=sc,
+                                  du=torch.empty(Ms, D, dtype=bf, device=dev), dO=torch.empty(Ms, D, dtype=bf, device=dev),
+                                  delta=torch.empty(2, B, H, N if Ms else 0, dtype=f32, device=dev))  # attention backward workspace: -delta, lse*log2e
         for li in range(len(fe.blocks) - 1, k0 - 1, -1):
-            blk, L = fe.blocks[li], st["layers"][li]
-            tail = L["tail"]
-            side = None if tail else side_all
-            if side is not None and (dxb_alt is None or dxb_alt.shape != dxb.shape):
-                dxb_alt = torch.empty_like(dxb)
-            R = B if tail else M
-            dz_, du_ = (dz[:R], du[:R]) if tail else (dz, du)
-            priv = private and not tail
-            plan = self._group_ok(M, D) if (priv and self.wgrad_group and wgrads) else ()
-            grouped = bool(plan)
-            # MLP
-            if priv:
-                held.append(dz)
-                dz = torch.empty_like(dz)
-                dz_ = dz
-            else:
-                before_write("dz")
-            hip.gemm_nt(dxb, self._bf(blk.mlp.fc2.weight, True), hip.EPI_GELU_BWD_BF16, dz_, aux=L["z"], **nt_kw)
-            wgrad_or_collect(dxb, L["h"], g(blk.mlp.fc2.weight), g(blk.mlp.fc2.bias), id(dxb), grouped)
-            hip.gemm_nt(dz_, self._bf(blk.mlp.fc1.weight, True), hip.EPI_PLAIN_BF16, du_, **nt_kw)
-            wgrad_or_collect(dz_, L["u2"], g(blk.mlp.fc1.weight), g(blk.mlp.fc1.bias), "dz", grouped)
-            if priv:
-                held.append(dxb)
-                dxb = torch.empty_like(dxb)
-            else:
-                if side is not None:
-                    dxb, dxb_alt = dxb_alt, dxb  # the fc2 weight gradient may still be reading the old one
-                before_write(id(dxb))
-            dsc = L.get("drop")  # this block's (attention, MLP) DropPath factors: the copy written here feeds its attention branch
-            hip.ln_bwd(du_, L["x_mid"], L["mean2"], L["rstd2"], blk.norm2.weight, dx, dx, dxb, g(blk.norm2.weight), g(blk.norm2.bias), R, D,
-                       **(dict(bf16_row_scale=dsc[0], rows_per_sample=R // B) if dsc else {}))
-            # attention
-            if tail:
-                dO_c = du[B:2 * B]  # scratch rows of the same buffer
-                hip.gemm_nt(dxb, self._bf(blk.attn.proj.weight, True), hip.EPI_PLAIN_BF16, dO_c, **nt_kw)
-                if wgrads:
-                    hip.gemm_tn_acc(dxb, L["o_c"], g(blk.attn.proj.weight), g(blk.attn.proj.bias))
-                dO.view(B, N, D)[:, 0].copy_(dO_c)  # only the CLS rows of dO are read (nq = 1)
-                hip.attn_bwd(L["qkv"], L["o"], dO, L["lse"], delta, dqkv, B, N, H, D // H, scale, nq=1, prescaled=ps)
-                dx_c = dx
-                dx = torch.zeros(M, D, dtype=f32, device=dev)  # the residual gradient reaches the block input at the CLS rows only
-                dx.view(B, N, D)[:, 0].copy_(dx_c)
-                dxb = torch.empty(M, D, dtype=bf, device=dev)
-            else:
-                hip.gemm_nt(dxb, self._bf(blk.attn.proj.weight, True), hip.EPI_PLAIN_BF16, dO, **nt_kw)
-                wgrad_or_collect(dxb, L["o"], g(blk.attn.proj.weight), g(blk.attn.proj.bias), id(dxb), grouped)
-                if priv:
-                    held.append(dqkv)
-                    dqkv = torch.empty_like(dqkv)
-                else:
-                    before_write("dqkv")
-                hip.attn_bwd(L["qkv"], L["o"], dO, L["lse"], delta, dqkv, B, N, H, D // H, scale, prescaled=ps)
-            hip.gemm_nt(dqkv, self._bf(blk.attn.qkv.weight, True), hip.EPI_PLAIN_BF16, du, **nt_kw)
-            wgrad_or_collect(dqkv, L["u1"], g(blk.attn.qkv.weight), g(blk.attn.qkv.bias), "dqkv", grouped)
-            if grouped:
-                launch_group(plan)
-            if priv:
-                held.append(dxb)
-                dxb = torch.empty_like(dxb)
-            else:
-                if side is not None:
-                    dxb, dxb_alt = dxb_alt, dxb
-                before_write(id(dxb))
-            below = st["layers"][li - 1].get("drop") if li > 0 else None  # the copy written here feeds the MLP branch of the block below
-            # At the first trainable block above a frozen prefix (li == k0 > 0) nobody reads what this launch writes for the block below (dx,
-            # and dxb with that block's DropPath factors): the loop ends here.  The launch stays as it is, for norm1's own weight and bias
-            # gradients come out of the same kernel, which reads the full-size dx as the residual gradient (the CLS-only tail's zero-filled
-            # one included); the two unread stores are 0.23 of the launch's 0.62 GB at the headline shape, once per backward, and the kernel has no form without them.
-            hip.ln_bwd(du, L["x_in"], L["mean1"], L["rstd1"], blk.norm1.weight, dx, dx, dxb, g(blk.norm1.weight), g(blk.norm1.bias), M, D,
-                       **(dict(bf16_row_scale=below[1], rows_per_sample=N) if below else {}))
-            if side is not None:
-                held.append(dict(L))  # the side stream may still be reading the saved activations
-            L.clear()
-            if self.wgrad_scratch_release or side is None:
-                # Everything in `held` — older layers' dz / dqkv / dxb and this layer's saved activations — has had its LAST reader queued
-                # (the block's weight-gradient launches above — grouped or one by one, they are all in their queue by now).  On ONE stream that
-                # is enough to hand the memory back, and it is done (peak scratch = one layer instead of depth x 0.7 GB).  With the
-                # second stream the hand-back needs record_stream (the allocator reuses the block only after that stream's queued work), and
-                # that is OFF by default: measured in round 4, the deferred frees make the caching allocator fall into its slow path once every
-                # few dozen steps — ONE step of ~1000 ms among 35 ms steps in 2 of 3 runs (gpurun r4u) — so the buffers are held until the
-                # streams join, as in round 3 (8.4 GB of scratch per backward for DiChaViT-S at bs 64, recycled step to step).
-                for t in held:
-                    for v in (t.values() if isinstance(t, dict) else (t,)):
-                        if side is not None and torch.is_tensor(v) and v.is_cuda:
-                            v.record_stream(side)
-                held.clear()
+            blk = fe.blocks[li]
+            below = st["layers"][li - 1].get("drop") if li > 0 else None
+            dx = self._block_backward(b, li, st["layers"][li], dx, below)
             if dp is not None:
-                if side is not None:
-                    # hand the bucket over FROM the side stream: the collective is ordered after the stream it is issued on, and the
-                    # side stream — made to wait for this layer's last LayerNorm-backward on the main stream — is behind every writer
-                    # of the slice; the main stream itself never waits for the weight gradients here
-                    ev = torch.cuda.Event()
-                    ev.record(main)
-                    side.wait_event(ev)
-                    with torch.cuda.stream(side):
-                        dp.grad_ready(ga, *self._range_of([blk.norm1.weight, blk.mlp.fc2.bias]))
-                else:
+                # with a side stream, hand the bucket over FROM it: the collective is ordered after the stream it is issued on, and the
+                # side stream — made to wait for this layer's last LayerNorm-backward on the main stream — is behind every writer
+                # of the slice; the main stream itself never waits for the weight gradients here
+                with sc.on_side():
                     dp.grad_ready(ga, *self._range_of([blk.norm1.weight, blk.mlp.fc2.bias]))
-        join()
-        held.clear()
+        sc.join()
         if fk is not None:
             return None, None, [self._gview(ga, p) if p.requires_grad else None for p in self._enc_params]
-        # --- tokeniser ---
+        return self._tokeniser_backward(st, dx, dstats, ga, g, dp)
+
+    def _block_backward(self, b, li, L, dx, below):
+        """The backward of encoder block li from its saved state L (emptied): from dx, the fp32 gradient of the stream after the block (its bf16
+        copy: b.sc.dxb), to that of the stream before it, which is returned (its copy: b.sc.dxb again).  below: block li - 1's DropPath factors."""
+        blk = self.feature_extractor.blocks[li]
+        B, N, M, g, nt_kw, sc = b.B, b.N, b.M, b.g, b.nt_kw, b.sc
+        D, H = self.dim, self.feature_extractor.num_heads
+        tail = L["tail"]
+        R = B if tail else M
+        sc.begin_block(tail)
+        # wgrad_group (with private scratch): a block's four weight-gradient products go out as ONE launch (dcv_gemm_tn_group) once the last of
+        # their operands (dqkv) exists: the tiles of all four fill the CUs, so each is split 7 ways over the token rows instead of 21-85 ways
+        if sc.private and self.wgrad_group and sc.wgrads:
+            sc.plan = self._group_ok(M, D)
+        du_ = b.du[:R] if tail else b.du
+        # MLP
+        dxb, dz = sc.dxb, sc.fresh("dz")
+        dz_ = dz[:R] if tail else dz
+        hip.gemm_nt(dxb, self._bf(blk.mlp.fc2.weight, True), hip.EPI_GELU_BWD_BF16, dz_, aux=L["z"], **nt_kw)
+        sc.wgrad(dxb, L["h"], g(blk.mlp.fc2.weight), g(blk.mlp.fc2.bias))
+        hip.gemm_nt(dz_, self._bf(blk.mlp.fc1.weight, True), hip.EPI_PLAIN_BF16, du_, **nt_kw)
+        sc.wgrad(dz_, L["u2"], g(blk.mlp.fc1.weight), g(blk.mlp.fc1.bias))
+        dxb = sc.fresh("dxb")
+        dsc = L.get("drop")  # this block's (attention, MLP) DropPath factors: the copy written here feeds its attention branch
+        hip.ln_bwd(du_, L["x_mid"], L["mean2"], L["rstd2"], blk.norm2.weight, dx, dx, dxb, g(blk.norm2.weight), g(blk.norm2.bias), R, D,
+                   **(dict(bf16_row_scale=dsc[0], rows_per_sample=R // B) if dsc else {}))
+        # attention
+        if tail:
+            dO_c = b.du[B:2 * B]  # scratch rows of the same buffer
+            hip.gemm_nt(dxb, self._bf(blk.attn.proj.weight, True), hip.EPI_PLAIN_BF16, dO_c, **nt_kw)
+            if sc.wgrads:
+                hip.gemm_tn_acc(dxb, L["o_c"], g(blk.attn.proj.weight), g(blk.attn.proj.bias))
+            b.dO.view(B, N, D)[:, 0].copy_(dO_c)  # only the CLS rows of dO are read (nq = 1)
+            hip.attn_bwd(L["qkv"], L["o"], b.dO, L["lse"], b.delta, sc.dqkv, B, N, H, D // H, _ATTN_SCALE, nq=1, prescaled=b.ps)
+            dx_c, dx = dx, torch.zeros(M, D, dtype=torch.float32, device=dx.device)  # the residual gradient reaches the block input at the CLS rows only
+            dx.view(B, N, D)[:, 0].copy_(dx_c)
+            sc.dxb = torch.empty(M, D, dtype=torch.bfloat16, device=dx.device)
+        else:
+            hip.gemm_nt(dxb, self._bf(blk.attn.proj.weight, True), hip.EPI_PLAIN_BF16, b.dO, **nt_kw)
+            sc.wgrad(dxb, L["o"], g(blk.attn.proj.weight), g(blk.attn.proj.bias))
+            hip.attn_bwd(L["qkv"], L["o"], b.dO, L["lse"], b.delta, sc.fresh("dqkv"), B, N, H, D // H, _ATTN_SCALE, prescaled=b.ps)
+        hip.gemm_nt(sc.dqkv, self._bf(blk.attn.qkv.weight, True), hip.EPI_PLAIN_BF16, b.du, **nt_kw)
+        sc.wgrad(sc.dqkv, L["u1"], g(blk.attn.qkv.weight), g(blk.attn.qkv.bias))
+        sc.launch_group()
+        # At the first trainable block above a frozen prefix (li == k0 > 0) nobody reads what this launch writes for the block below (dx,
+        # and dxb with that block's DropPath factors): the loop ends here.  The launch stays as it is, for norm1's own weight and bias
+        # gradients come out of the same kernel, which reads the full-size dx as the residual gradient (the CLS-only tail's zero-filled
+        # one included); the two unread stores are 0.23 of the launch's 0.62 GB at the headline shape, once per backward, and the kernel has no form without them.
+        hip.ln_bwd(b.du, L["x_in"], L["mean1"], L["rstd1"], blk.norm1.weight, dx, dx, sc.fresh("dxb"), g(blk.norm1.weight), g(blk.norm1.bias), M, D,
+                   **(dict(bf16_row_scale=below[1], rows_per_sample=N) if below else {}))  # the copy feeds the MLP branch of the block below
+        sc.end_block(L)
+        return dx
+
+    def _tokeniser_backward(self, st, dx, dstats, ga, g, dp):
+        """From the gradient of the token stream [M, D]: (dE, dpos, parameter gradients); the input-image gradient goes to st["dx_out"]."""
+        fe, D, dev = self.feature_extractor, self.dim, dx.device
+        pe, wgrads = fe.patch_embed, ga is not None
+        B, C, n, N = st["B"], st["C"], st["n"], st["N"]
+        T = C * n
+        bf, f32 = torch.bfloat16, torch.float32
         if st.get("keep_dev") is not None:  # adjoint of the token gather: dropped tokens receive no gradient
             Nf = st["N_full"]
             dxf = torch.zeros(B * Nf, D, dtype=f32, device=dev)
             hip.gather_tokens(dx, st["keep_dev"], dxf, B, Nf, N, D, scatter=True)
             dx = dxf
-        pe = fe.patch_embed
         dYl = None
         if st["want_ortho"] and dstats is not None:
             dYl = torch.empty(B * T, D, dtype=f32, device=dev)
@@ -1359,10 +1316,7 @@ class DiChaViT(nn.Module):
         if dp is not None:
             dp.grad_ready(ga, *self._range_of([fe.cls_token, pe.proj.bias]))
             dp.flush()
-        grads = []
-        for p in self._enc_params:
-            grads.append(self._gview(ga, p) if (wgrads and p.requires_grad) else None)
-        return dE, dpos, grads
+        return dE, dpos, [self._gview(ga, p) if (wgrads and p.requires_grad) else None for p in self._enc_params]
 
     def _group_ok(self, M, D):
         """How a block's four weight-gradient products (in the order the backward produces their operands: fc2, fc1, proj, qkv) are grouped
@@ -1427,15 +1381,13 @@ class DiChaViT(nn.Module):
         extra = 0
         if want_ortho:
             extra = extra + lam_o * self._ortho_from_stats(stats, C, n)
-        if lam_p > 0 and (self.training or True):
-            # the reference evaluates the proxy term in eval mode too and discards it; skip it there
-            if self.training:
-                prox = pe.channel_emb_proxies.index_select(0, self._index_tensor(cur_channels, torch.int64, x.device))  # global ids (:401)
-                if (self.fused_proxy_loss and prox.dtype == torch.float32 and channel_embed.dtype == torch.float32
-                        and hip.proxy_loss_supported(C, self.dim)):
-                    extra = extra + lam_p * _ChannelProxyLossFn.apply(prox, channel_embed, float(pe.channel_scale))
-                else:
-                    extra = extra + lam_p * _proxy_loss(prox, channel_embed, torch.eye(C, device=x.device), float(pe.channel_scale))
+        if lam_p > 0 and self.training:  # the reference evaluates the proxy term in eval mode too and discards it; skipped there
+            prox = pe.channel_emb_proxies.index_select(0, self._index_tensor(cur_channels, torch.int64, x.device))  # global ids (:401)
+            if (self.fused_proxy_loss and prox.dtype == torch.float32 and channel_embed.dtype == torch.float32
+                    and hip.proxy_loss_supported(C, self.dim)):
+                extra = extra + lam_p * _ChannelProxyLossFn.apply(prox, channel_embed, float(pe.channel_scale))
+            else:
+                extra = extra + lam_p * _proxy_loss(prox, channel_embed, torch.eye(C, device=x.device), float(pe.channel_scale))
         out = self.classifer_head(feat)  # :855
         if self.training:
             if isinstance(extra, int) and extra == 0:
@@ -1510,12 +1462,33 @@ class DiChaViT(nn.Module):
                                      lam_p=lam_p, pos_tab=pos_tab, ch_idx_dev=ch_idx_dev, keep=keep, tok=tok, E_tok=E_tok, scale=cur_scale,
                                      shift=cur_shift)
 
-    def _probe_attention(self, x, chunk_name, layer_idx, query_rows):
-        """ChannelVisionTransformer.get_last_selfattention: the tokens as forward() prepares them, then blocks 0 .. layer through _run_forward's
-        probe.  DataParallel's begin_forward() is not called: no gradient leaves this path."""
+    # ---------------------------------------------------------------------------------------
+    # inspection calls (ChannelVisionTransformer.get_*): loops of their own over the forward's pieces
+    # ---------------------------------------------------------------------------------------
+    @contextlib.contextmanager
+    def _inspection_tokens(self, x, chunk_name, training_chunks=None, new_channel_init=None):
+        """What the three inspection calls start with: autocast off, no_grad, the input checks and the tokens as forward() prepares them.
+        DataParallel's begin_forward() is not called: no gradient leaves these paths."""
         with torch.autocast(device_type="cuda", enabled=False), torch.no_grad():
             self._check_input(x)
-            tk = self._prepare_tokens(x, chunk_name, None, None)
+            yield self._prepare_tokens(x, chunk_name, training_chunks, new_channel_init)
+
+    def _inspection_tokenise(self, tk):
+        """The tokeniser on scratch operand copies: the model's own (_bf16, _bf16_t, _qbias) and _sr_seed are left alone — a training
+        forward's backward may still read them — and round-to-nearest straight copies are cast into private buffers instead.  Returns
+        (f, the residual stream) as _tokenise does."""
+        wbuf, qbias = torch.empty_like(self._bf16), torch.empty_like(self._qbias)
+        hip.cast_bf16(self._arena, wbuf, self._enc_size)
+        if self.attn_prescaled:
+            hip.cast_scaled_ranges(self._arena, wbuf, qbias, self._qdesc, self._qdesc.shape[0], 64, _Q_PRESCALE)
+        f, xcur, _, _ = self._tokenise(tk.x, tk.ch_idx_dev, tk.C, tk.E_tok, tk.pos_tab, False, tk.keep, tk.scale, tk.shift, tk.tok, wbuf, qbias)
+        return f, xcur
+
+    def _probe_attention(self, x, chunk_name, layer_idx, query_rows):
+        """ChannelVisionTransformer.get_last_selfattention: blocks < layer run as the forward runs them; the probed block stops after its
+        norm1, qkv GEMM and the attention of its query rows (for their LSE), from which dcv_attn_probs_rows writes the probabilities
+        [B, H, rows, N] once.  No later block runs."""
+        with self._inspection_tokens(x, chunk_name) as tk:
             depth = len(self.feature_extractor.blocks)
             layer_idx = int(layer_idx)
             if not -depth <= layer_idx < depth:
@@ -1524,32 +1497,64 @@ class DiChaViT(nn.Module):
             rows = N if query_rows is None else int(query_rows)
             if not 1 <= rows <= N:
                 raise ValueError(f"query_rows={query_rows}: expected 1 <= query_rows <= {N} (the tokens this block sees)")
-            return self._run_forward(tk.x, tk.ch_idx_dev, tk.C, tk.E_tok, tk.pos_tab, False, save=False, keep=tk.keep, st_scale=tk.scale,
-                                     st_shift=tk.shift, tok=tk.tok, probe=(layer_idx % depth, rows))
+            f, xcur = self._inspection_tokenise(tk)
+            pre_ln = None
+            for bi in range(layer_idx % depth):
+                xcur, pre_ln, _ = self._block_forward(f, bi, xcur, pre_ln)
+            a = self._block_attention(f, layer_idx % depth, xcur, pre_ln, nq=rows)
+            probs = torch.empty(f.B, f.H, rows, N, dtype=torch.float32, device=f.dev)
+            hip.attn_probs(a["qkv"], a["lse"], probs, f.B, N, f.H, f.D // f.H, _ATTN_SCALE, nq=rows, prescaled=f.ps)
+            return probs
 
     def _probe_layers(self, x, chunk_name, training_chunks, new_channel_init, blocks, pool):
-        """ChannelVisionTransformer.get_intermediate_layers: the tokens as forward() prepares them, then blocks 0 .. blocks[-1] through
-        _run_forward's capture.  DataParallel's begin_forward() is not called: no gradient leaves this path."""
-        with torch.autocast(device_type="cuda", enabled=False), torch.no_grad():
-            self._check_input(x)
-            tk = self._prepare_tokens(x, chunk_name, training_chunks, new_channel_init)
+        """ChannelVisionTransformer.get_intermediate_layers: blocks 0 .. blocks[-1] (ascending), every one on all rows (no CLS-only tail);
+        the final norm of the stream after each listed block is launched right after that block — the stream is updated in place, so the
+        capture is stream-ordered before the next block overwrites it.  pool=None: [B, N, D] (dcv_ln_fwd, fp32 output); pool="channel":
+        [B, 1 + C, D] (dcv_ln_pool_channels)."""
+        with self._inspection_tokens(x, chunk_name, training_chunks, new_channel_init) as tk:
             if pool == "channel" and tk.keep is not None:
                 raise ValueError("pool='channel' needs every channel's n_p patch tokens: with dropout_tokens_hcs active in train mode the channel "
                                  "segments are ragged (pool=None returns the kept tokens)")
-            return self._run_forward(tk.x, tk.ch_idx_dev, tk.C, tk.E_tok, tk.pos_tab, False, save=False, keep=tk.keep, st_scale=tk.scale,
-                                     st_shift=tk.shift, tok=tk.tok, capture=(blocks, pool))
+            fe = self.feature_extractor
+            f, xcur = self._inspection_tokenise(tk)
+            pre_ln, captured = None, []
+            for bi in range(blocks[-1] + 1):
+                # a capture that ends at block bi still launches the fused fc2 + next-norm1 form although block bi + 1 never runs: the stream of
+                # block bi must come from the same kernel whether or not later blocks are requested (n=4 equals four single-index calls bit for
+                # bit), at the cost of one unused norm1 output in the epilogue
+                xcur, pre_ln, _ = self._block_forward(f, bi, xcur, pre_ln)
+                if bi not in blocks:
+                    continue
+                if pool == "channel":
+                    cap = torch.empty(f.B, 1 + f.C, f.D, dtype=torch.float32, device=f.dev)
+                    hip.ln_pool_channels(xcur, fe.norm.weight, fe.norm.bias, cap, f.B, f.C, f.n, f.D, LN_EPS)
+                else:
+                    cap = torch.empty(f.B, f.N, f.D, dtype=torch.float32, device=f.dev)
+                    hip.ln_fwd(xcur, fe.norm.weight, fe.norm.bias, cap, None, None, f.M, f.D, LN_EPS)
+                captured.append(cap)
+            return captured
 
     def _probe_channel_attention(self, x, chunk_name, training_chunks, new_channel_init, blocks, queries):
-        """ChannelVisionTransformer.get_channel_attention: the tokens as forward() prepares them, then blocks 0 .. blocks[-1] through
-        _run_forward's chan_attn.  DataParallel's begin_forward() is not called: no gradient leaves this path."""
-        with torch.autocast(device_type="cuda", enabled=False), torch.no_grad():
-            self._check_input(x)
-            tk = self._prepare_tokens(x, chunk_name, training_chunks, new_channel_init)
+        """ChannelVisionTransformer.get_channel_attention: blocks 0 .. blocks[-1] (ascending), every one on all rows; a listed block runs its
+        ordinary attention and then dcv_attn_channel_mass on its qkv and LSE — queries="channel": [B, H, 1 + C, 1 + C], "token":
+        [B, H, N, 1 + C], the key segments by (C, n).  The rest of the last listed block and every later block never run."""
+        with self._inspection_tokens(x, chunk_name, training_chunks, new_channel_init) as tk:
             if tk.keep is not None:
                 raise ValueError("get_channel_attention needs every channel's n_p patch tokens: with dropout_tokens_hcs active in train mode the "
                                  "channel segments are ragged")
-            return self._run_forward(tk.x, tk.ch_idx_dev, tk.C, tk.E_tok, tk.pos_tab, False, save=False, keep=None, st_scale=tk.scale,
-                                     st_shift=tk.shift, tok=tk.tok, chan_attn=(blocks, queries))
+            f, xcur = self._inspection_tokenise(tk)
+            B, H, N, C = f.B, f.H, f.N, f.C
+            pre_ln, captured = None, []
+            for bi in range(blocks[-1] + 1):
+                a = self._block_attention(f, bi, xcur, pre_ln)
+                if bi in blocks:
+                    cap = torch.empty((B, H, N, 1 + C) if queries == "token" else (B, H, 1 + C, 1 + C), dtype=torch.float32, device=f.dev)
+                    hip.attn_channel_mass(a["qkv"], a["lse"], B, N, H, f.D // H, _ATTN_SCALE, C, f.n, prescaled=f.ps,
+                                          **{"tok" if queries == "token" else "ch": cap})
+                    captured.append(cap)
+                if bi < blocks[-1]:
+                    xcur, pre_ln, _ = self._block_residuals(f, bi, xcur, a)
+            return captured
 
     def _ortho_from_stats(self, stats, C, n):
         """loss_fn.py:44-59 on the per-image (pos_sum, neg_sum)."""

@@ -1767,9 +1767,9 @@ def test_dp_async_collectives_emulated_on_one_gpu(gpu_device, grad_dtype, overla
 
 @pytest.mark.parametrize("private,group,two_streams", [(False, False, True), (True, False, True), (False, False, False), (True, True, False)])
 def test_backward_scratch_and_grouping_fallbacks(gpu_device, private, group, two_streams):
-    """The backward's switches (dichavit.py, _run_backward_body): per-layer scratch or two shared buffers with reader waits, a block's four weight
+    """The backward's switches (dichavit.py, _BackwardScratch and _block_backward): per-layer scratch or two shared buffers with reader waits, a block's four weight
     gradients in one grouped launch or in four, one stream or two.  Every combination is the same arithmetic up to the split of the weight-gradient
-    sums over the token rows: the gradients must agree with the default configuration's (private scratch, grouped, two streams) to fp32 rounding."""
+    sums over the token rows: the gradients must agree with the default configuration's (private scratch, grouped, one stream) to fp32 rounding."""
     meta, a = load_golden("so2sat_s")
     x, y = orc.make_batch(meta["seed"] + 1, meta["B"], meta["C_in"], meta["img"], meta["num_classes"])
     grads = {}
@@ -1792,7 +1792,7 @@ def test_backward_scratch_and_grouping_fallbacks(gpu_device, private, group, two
 
 
 def test_weight_gradients_on_second_stream_match_one_stream(gpu_device):
-    """The backward runs the weight-gradient GEMMs on a second HIP stream (dichavit.py, _run_backward_body: wgrad_stream).  Same
+    """The backward runs the weight-gradient GEMMs on a second HIP stream (dichavit.py, _BackwardScratch: wgrad_stream).  Same
     kernels on the same operands as the one-stream backward: every gradient must agree up to the order of the fp32 atomic adds of
     the split reductions (each launch's own order is not fixed either), over several steps (the scratch buffers the side stream
     reads are reused every layer and every step) and against the fp64 oracle."""
