@@ -355,6 +355,34 @@ class ChannelVisionTransformer(_Holder):
             raise ValueError(f"queries={queries!r}: expected 'channel' or 'token'")
         return self._linked_owner("get_channel_attention")._probe_channel_attention(x, chunk, training_chunks, new_channel_init, blocks, queries)
 
+    def get_attention_rollout(self, x, extra_tokens={}, *, chunk="", training_chunks=None, new_channel_init=None, start_layer=0, residual=0.5,
+                              start=None):
+        """Which patches of which channels does the CLS prediction rest on, through all blocks: attention rollout (Abnar & Zuidema, 2020) with
+        mean head fusion, as one fp32 [B, N] tensor on x's device, detached (an inspection API: no gradient).  No counterpart in the reference, whose
+        users call get_last_selfattention once per block, average the heads and multiply the [N, N] matrices themselves.  With L blocks,
+            r = start^T . A~_{L-1} . A~_{L-2} ... A~_{start_layer},     A~_l = residual I + (1 - residual) mean_h A_l
+        (A_l the softmax attention of block l): the row of the rollout matrix that belongs to `start`, pushed through the blocks from the last one
+        down — one dcv_attn_rollout_step per block on that block's qkv and LSE, kept from ONE forward; no N x N matrix is ever written.  The
+        tokens are prepared as forward() prepares them (see get_intermediate_layers, whose parameters chunk, training_chunks and new_channel_init
+        are); HCS sampling and token drop in train mode work as they are: N is the tokens this forward saw.
+
+        The result: every row sums to sum(start) (1 by default); r[:, 0] is the mass left on CLS; token 1 + c * n_p + i = patch i of channel c,
+        channels in this forward's token order (the chunk's, or in train mode the HCS subset's), so without token drop
+        r[:, 1:].view(B, C, gh, gw) are the per-channel patch maps.
+        start_layer: an int in [-depth, depth), negative counts from the end: the blocks start_layer .. depth - 1 are rolled (0: all of them).
+        residual: in [0, 1): the weight of the identity (the residual connection) in every block; 0.5 with start_layer=0 is the paper's rollout.
+        start: None — one-hot CLS — or an fp32 [B, N] tensor on x's device, >= 0 (checked with one host read): the query weights to roll.
+        Memory: the qkv and LSE of the rolled blocks are kept until the walk down (231 MB per block at B 64, 8 channels, 224 x 224, ViT-S)."""
+        depth = len(self.blocks)
+        if isinstance(start_layer, bool) or not isinstance(start_layer, int) or not -depth <= start_layer < depth:
+            raise ValueError(f"start_layer={start_layer!r}: expected an int in [{-depth}, {depth})")
+        if isinstance(residual, bool) or not isinstance(residual, (int, float)) or not 0.0 <= residual < 1.0:
+            raise ValueError(f"residual={residual!r}: expected a number in [0, 1)")
+        if start is not None and not isinstance(start, torch.Tensor):
+            raise ValueError(f"start: expected None or an fp32 [B, N] tensor, got {type(start).__name__}")
+        return self._linked_owner("get_attention_rollout")._probe_rollout(x, chunk, training_chunks, new_channel_init, start_layer % depth,
+                                                                          float(residual), start)
+
     @staticmethod
     def _init_weights(m):  # dichavit.py:509-516
         if isinstance(m, nn.Linear):
@@ -1555,6 +1583,40 @@ class DiChaViT(nn.Module):
                 if bi < blocks[-1]:
                     xcur, pre_ln, _ = self._block_residuals(f, bi, xcur, a)
             return captured
+
+    def _probe_rollout(self, x, chunk_name, training_chunks, new_channel_init, start_layer, residual, start):
+        """ChannelVisionTransformer.get_attention_rollout: every block on all rows, the last one up to its attention only; the qkv and LSE of
+        blocks start_layer .. depth - 1 are kept, then walked from the last block down with two ping-pong [B, N] buffers, one
+        dcv_attn_rollout_step per block.  Blocks below start_layer keep nothing."""
+        with self._inspection_tokens(x, chunk_name, training_chunks, new_channel_init) as tk:
+            depth = len(self.feature_extractor.blocks)
+            B = tk.x.shape[0]
+            N = len(tk.keep) if tk.keep is not None else tk.C * tk.n + 1
+            if start is None:
+                r = torch.zeros(B, N, dtype=torch.float32, device=tk.x.device)
+                r[:, 0] = 1.0
+            else:
+                if start.dtype != torch.float32 or tuple(start.shape) != (B, N) or start.device != tk.x.device:
+                    raise ValueError(f"start: expected an fp32 tensor of shape ({B}, {N}) (the tokens this forward sees) on {tk.x.device}, got "
+                                     f"{start.dtype} {tuple(start.shape)} on {start.device}")
+                if not bool((start >= 0).all()):  # one host read: also refuses NaN
+                    raise ValueError("start: every weight must be >= 0")
+                r = start.detach().contiguous().clone()
+            f, xcur = self._inspection_tokenise(tk)
+            pre_ln, kept = None, []
+            for bi in range(depth):
+                a = self._block_attention(f, bi, xcur, pre_ln)
+                if bi >= start_layer:
+                    kept.append((a["qkv"], a["lse"]))
+                if bi < depth - 1:
+                    xcur, pre_ln, _ = self._block_residuals(f, bi, xcur, a)
+                del a
+            nxt = torch.empty_like(r)
+            while kept:
+                qkv, lse = kept.pop()  # the last block first; a block's qkv is released as soon as its step is queued
+                hip.attn_rollout_step(qkv, lse, r, nxt, f.B, f.N, f.H, f.D // f.H, _ATTN_SCALE, residual, prescaled=f.ps)
+                r, nxt = nxt, r
+            return r
 
     def _ortho_from_stats(self, stats, C, n):
         """loss_fn.py:44-59 on the per-image (pos_sum, neg_sum)."""

@@ -62,6 +62,8 @@ _SIGS = {
     "dcv_attn_channel_mass_ws_floats": ([_i, _i, _i, _i], _l),
     "dcv_attn_channel_mass": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _i, _vp, _l, _vp], _i),
     "dcv_attn_channel_mass_ps": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _l, _vp], _i),
+    "dcv_attn_rollout_step": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _vp], _i),
+    "dcv_attn_rollout_step_ps": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp], _i),
     "dcv_im2col_bf16": ([_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp], _i),
     "dcv_patch_bwd": ([_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp], _i),
     "dcv_patch_dgrad": ([_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp], _i),
@@ -465,6 +467,22 @@ def attn_channel_mass(qkv, lse, B, N, H, hd, scale, C, n_p, tok=None, ch=None, p
         else:
             rc = lib.dcv_attn_channel_mass(_p(qkv), _p(lse), _p(tok), _p(ch), B, N, H, hd, float(scale), C, n_p, _p(ws), nws, _stream())
     _check(rc, "dcv_attn_channel_mass")
+
+
+def attn_rollout_step(qkv, lse, w, out, B, N, H, hd, scale, alpha, prescaled=False):
+    """One attention-rollout step over one block, heads averaged, from qkv and the forward's lse (include/dcv.h: dcv_attn_rollout_step):
+    out [B, N] fp32 = w^T (alpha I + (1 - alpha) mean_h P) for w [B, N] fp32 >= 0.  out must not overlap w; alpha in [0, 1).  prescaled: as
+    attn_probs."""
+    _req(qkv, torch.bfloat16, "qkv"); _req(lse, torch.float32, "lse"); _req(w, torch.float32, "w"); _req(out, torch.float32, "out")
+    if qkv.numel() < B * N * 3 * H * hd or lse.numel() < B * H * N or w.numel() < B * N or out.numel() < B * N:
+        raise ValueError("attn_rollout_step: qkv holds B*N*3*H*hd elements, lse B*H*N floats, w and out B*N")
+    with _timer(lambda: (f"attn_rollout_kernel<{'true' if prescaled else 'false'}>", f"B{B} N{N} H{H}", 2.0 * B * H * N * N * hd, None,
+                         2.0 * B * N * 2 * H * hd + 4.0 * B * N * (H + 2))):
+        if prescaled:
+            rc = load().dcv_attn_rollout_step_ps(_p(qkv), _p(lse), _p(w), _p(out), B, N, H, hd, float(alpha), _stream())
+        else:
+            rc = load().dcv_attn_rollout_step(_p(qkv), _p(lse), _p(w), _p(out), B, N, H, hd, float(scale), float(alpha), _stream())
+    _check(rc, "dcv_attn_rollout_step")
 
 
 def im2col(x, ch_idx, out, B, Ct, C, H, W, P, scale=None, shift=None):

@@ -224,6 +224,18 @@ int dcv_attn_channel_mass(const void* qkv, const float* lse, float* tok, float* 
                           float* ws, long ws_floats, void* stream);
 int dcv_attn_channel_mass_ps(const void* qkv, const float* lse, float* tok, float* ch, int B, int N, int H, int head_dim, int C, int n_p, float* ws,
                              long ws_floats, void* stream);
+/* One step of attention rollout over one block, heads averaged (ChannelVisionTransformer.get_attention_rollout; Abnar & Zuidema's rollout is the
+ * row vector pushed through the blocks from the last one down): w, out [B,N] f32, w >= 0,
+ *     out[b,k] = alpha w[b,k] + (1 - alpha) / H * sum over h and q of w[b,q] P[b,h,q,k],    P as dcv_attn_probs_rows forms it
+ * i.e. out = w^T (alpha I + (1 - alpha) mean_h P); sum_k out = sum_k w.  qkv / lse (all N rows read) as dcv_attn_fwd_rows(_ps) produced them; the
+ * _ps form takes the pre-scaled q.  Summed in fp32; no [., N, N] array is written and there is no workspace.  No atomics: the order of every add is
+ * fixed by (N, H) — bitwise reproducible, and out[b,k] does not depend on the other keys.  Every out[b,k], k < N, is written once and nothing else.
+ * out must not overlap w (every workgroup reads all of w[b,:]): DCV_ERR_UNSUPPORTED, as is alpha outside [0, 1) or NaN.  lse, w, out 4-byte
+ * aligned.  A query with w = 0 contributes exactly nothing. */
+int dcv_attn_rollout_step(const void* qkv, const float* lse, const float* w, float* out, int B, int N, int H, int head_dim, float scale, float alpha,
+                          void* stream);
+int dcv_attn_rollout_step_ps(const void* qkv, const float* lse, const float* w, float* out, int B, int N, int H, int head_dim, float alpha,
+                             void* stream);
 
 /* x [B,Ct,H,W] f32 (x_is_u8 == 0: normalised images, the reference's batch format) or u8 (raw pixels), ch_idx int32[C]
  * (device) -> bf16 [B*C*(H/P)*(W/P), P*P] patch rows (dichavit.py:134/210,377).  scale/shift f32[C] (nullable, indexed by
