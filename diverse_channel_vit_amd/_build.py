@@ -9,7 +9,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libdcv_hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=fast", "-Wall", "-Wno-unused-function"]
+FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=fast", "-Wall"]
 # per-file extras.  attn: keep MFMA accumulators in arch VGPRs (gfx950's register file is unified) — the
 # softmax touches them with VALU every tile and the AGPR form costs ~250 v_accvgpr moves per key tile.
 EXTRA = {"attn.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],

@@ -36,13 +36,6 @@ struct ChMassArgs {
 
 constexpr int CHM_QTILE = 128;  // query rows per workgroup (4 waves x 32)
 
-// x of lane l + x of lane l ^ 32, always as (lower half) + (upper half): the same bits in both halves
-__device__ __forceinline__ float sum_halves(float x) {
-    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-    const u32x2 r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-
 template <bool PS>
 __global__ __launch_bounds__(256) void attn_channel_mass_kernel(ChMassArgs a) {
     __shared__ __attribute__((aligned(16))) char sK[64 * 128];

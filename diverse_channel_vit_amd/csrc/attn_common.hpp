@@ -107,6 +107,12 @@ __device__ __forceinline__ float max_halves(float x) {
     asm("v_max_f32 %0, %1, %2" : "=v"(m) : "v"(r[0]), "v"(r[1]));
     return m;
 }
+// x of lane l + x of lane l ^ 32, always as (lower half) + (upper half): the same bits in both halves
+__device__ __forceinline__ float sum_halves(float x) {
+    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+    const u32x2 r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
+    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+}
 
 __device__ __forceinline__ void zero_acc(f32x16& x) {
 #pragma unroll

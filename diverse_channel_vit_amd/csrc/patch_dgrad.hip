@@ -147,19 +147,6 @@ void pd_launch(const void* dY, const void* Wb, const int* ch_idx, const float* s
 
 }  // namespace
 
-// CU count of the current device, queried once per device (as gemm.hip's; no allocation, no sync)
-static int pd_cu_count() {
-    static int cached[16];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = 0;
-    int n = __atomic_load_n(&cached[dev], __ATOMIC_RELAXED);
-    if (n <= 0) {
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-        __atomic_store_n(&cached[dev], n, __ATOMIC_RELAXED);
-    }
-    return n;
-}
-
 extern "C" int dcv_patch_dgrad(const void* dY, const void* W_bf16, const int* ch_idx, const float* scale, float* dx, int B, int Ct, int C,
                                int H, int W, int P, int D, void* stream) {
     if (!dY || !W_bf16 || !ch_idx || !dx) return DCV_ERR_NULL;
@@ -168,7 +155,7 @@ extern "C" int dcv_patch_dgrad(const void* dY, const void* W_bf16, const int* ch
     if ((P != 8 && P != 16) || (D != 192 && D != 384 && D != 768)) return DCV_ERR_UNSUPPORTED;
     if (((uintptr_t)dY & 15) || ((uintptr_t)dx & 15)) return DCV_ERR_ALIGN;
     hipStream_t s = (hipStream_t)stream;
-    const int cus = pd_cu_count();
+    const int cus = dcv_cu_count();
     // Q: pixel columns of W^T one workgroup holds in LDS (Q * (D + 8) * 2 bytes <= 100 KB)
     if (P == 16) {
         if (D == 192) pd_launch<16, 192, 256>(dY, W_bf16, ch_idx, scale, dx, B, Ct, C, H, W, cus, s);

@@ -57,6 +57,16 @@ def test_product_never_imports_oracle():
             assert "import oracle" not in txt and "from oracle" not in txt, f
 
 
+def test_no_header_defines_a_kernel():
+    """Every translation unit emits its own copy of a kernel that a header defines (the det-reduce kernels were once compiled 15 times):
+    kernels live in .hip files, headers carry declarations and inline device helpers only."""
+    csrc = os.path.join(ROOT, "diverse_channel_vit_amd", "csrc")
+    headers = [f for f in os.listdir(csrc) if f.endswith(".hpp")]
+    assert headers
+    for f in headers:
+        assert "__global__" not in open(os.path.join(csrc, f)).read(), f
+
+
 def test_gemm_tile_choice_rules():
     """dcv_gemm_nt_pick / dcv_gemm_tn_pick are host logic (no GPU call): the automatic tile choice for the headline step's products
     (measured per shape in profiles/r02_x4_* and r02_x10_*) and the refusal of an illegal forced tile."""

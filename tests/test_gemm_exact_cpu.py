@@ -1,4 +1,4 @@
-"""The premises of tests/test_gemm_exact_gpu.py, without a GPU: the launch plans restated there (from csrc/gemm.hip) against hand-checked
+"""The premises of tests/test_gemm_exact_gpu.py, without a GPU: the launch plans restated there (from csrc/gemm_nt.hip and csrc/gemm_tn.hip) against hand-checked
 values and the library's host-side answers, every regime the case tables are meant to reach, the exactness condition and the share of
 exact bf16 ties on every case's generated inputs, the pads of the padded layouts, and a float32 emulation of the GELU epilogue that
 shows where the slack of the one toleranced check comes from.  The library is loaded for its host logic only (tile picks, the 256 x 384
@@ -69,7 +69,7 @@ def test_tn_plan_restated(lib):
         assert lib.dcv_gemm_tn_group_ws_floats(C.cast(arr, C.c_void_p), len(T.GROUP_ITEMS), M) == T.tn_group_plan(T.GROUP_ITEMS, M)[3], M
     # regimes: (name, predicate) — each must hold for a row of BOTH tables unless it exists on one tile only
     plans = {c: T.tn_plan(c.tile, c.M, c.P, c.Q) for c in T.TN_CASES}
-    ring = {N_: 2, W_: 4}  # csrc/gemm.hip: gemm_tn_kernel double-buffers, T3_STAGES = 4
+    ring = {N_: 2, W_: 4}  # csrc/gemm_tn.hip: gemm_tn_kernel double-buffers, T3_STAGES = 4
     regimes = {
         "ragged last stage": lambda c, p: p.last_rows % p.stage != 0,
         "last split shorter than the others": lambda c, p: p.splits > 1 and p.last_rows < p.mps,
@@ -173,7 +173,7 @@ def test_tie_share_and_ulp_helpers():
 
 
 def _gelu_parts2_f32(z):
-    """csrc/gemm.hip gelu_parts2 in float32: every multiply-add one fused operation (-ffp-contract=fast), rcp and exp2 rounded correctly
+    """csrc/gemm_nt.hip gelu_parts2 in float32: every multiply-add one fused operation (-ffp-contract=fast), rcp and exp2 rounded correctly
     (the hardware's are within 1 ulp)"""
     f = np.float32
 

@@ -1,4 +1,4 @@
-"""The GEMM kernels of csrc/gemm.hip bit for bit: exact operands, padded layouts, guard rows.
+"""The GEMM kernels of csrc/gemm_nt.hip and csrc/gemm_tn.hip bit for bit: exact operands, padded layouts, guard rows.
 
 Two gaps of the older GEMM tests are closed here.
 
@@ -44,7 +44,7 @@ NAN = float("nan")
 EPI_BIAS, EPI_GELU, EPI_RESID, EPI_PLAIN, EPI_GELU_BWD, EPI_PATCH = range(6)           # include/dcv.h DCV_EPI_*
 TILE_AUTO, TILE_NARROW, TILE_WIDE, TILE_PAIR, TILE_ALT, TILE_WS, TILE_AUTO_WS = range(7)  # include/dcv.h DCV_TILE_*
 ERR_SHAPE, ERR_ALIGN = -1, -2
-WS_M_MIN = 8192   # csrc/gemm.hip: DCV_WS_M_MIN
+WS_M_MIN = 8192   # csrc/gemm_nt.hip: DCV_WS_M_MIN
 FACTORS = (1.25, 0.0, 2.0, 0.5, 1.0)  # per-sample branch factors (DropPath's keep_b / keep_prob)
 
 # pads (in elements) per layout: bf16 operands (A, W, Y, X, the bf16 aux) share `op`; every output has its own
@@ -106,7 +106,7 @@ NtWalk = namedtuple("NtWalk", "tiles_m tiles_n grid rounds last_round stages")
 
 
 def nt_walk(tile, M, N, K, cap, cus=CUS):
-    """The static tile walks of the NARROW / PAIR kernels: csrc/gemm.hip gemm_nt_kernel (tiles of 256 x 128, `L = k * G + pos`) with the
+    """The static tile walks of the NARROW / PAIR kernels: csrc/gemm_nt.hip gemm_nt_kernel (tiles of 256 x 128, `L = k * G + pos`) with the
     grid of dcv_gemm_nt_ex (`grid = min(tiles, cap)`), gemm_nt_pair_kernel (128 x 128, `gp = min(tiles, 2 * cap)`); K in 64-wide stages."""
     bm, per_cu = (256, 1) if tile == TILE_NARROW else (128, 2)
     tm, tn = _cdiv(M, bm), _cdiv(N, 128)
@@ -130,7 +130,7 @@ TnPlan = namedtuple("TnPlan", "tiles_q tiles planned mps splits stage nk_max las
 
 
 def tn_plan(tile, M, P, Q, cus=CUS):
-    """csrc/gemm.hip tn_plan and the workspace layout of tn_launch / dcv_gemm_tn_det_ws_floats: `planned` splits of the token rows (one
+    """csrc/gemm_tn.hip tn_plan and the workspace layout of tn_launch / dcv_gemm_tn_det_ws_floats: `planned` splits of the token rows (one
     resident round: 2 workgroups per CU for the 128 x 128 kernel, 1 for the 384 x 128 one; at most one per stage), `mps` rows per split
     rounded up to whole stages, `splits` = the leading ones that have rows."""
     if tile == TILE_WIDE:
@@ -148,7 +148,7 @@ def tn_plan(tile, M, P, Q, cus=CUS):
 
 
 def tn_group_plan(items, M, cus=CUS):
-    """csrc/gemm.hip tn_group_plan: every product split the same way, `sp = min(cus / all tiles, stages)`; workspace per item
+    """csrc/gemm_tn.hip tn_group_plan: every product split the same way, `sp = min(cus / all tiles, stages)`; workspace per item
     [splits][P Q] then [splits * Q / 128][P].  Returns (tiles, mps, splits, ws floats)."""
     tiles = sum((P // 384) * (Q // 128) for P, Q, _ in items)
     sp = min(cus // tiles, _cdiv(M, 32))

@@ -128,7 +128,7 @@ def test_gemm_nt_384_wide_tiles(hip, M, N, K):
 
 # The headline step's GEMMs: M = 64 x 1569 = 100 416 token rows.  Both NT kernels are PERSISTENT: one workgroup per CU walks
 # 1 179 - 4 716 output tiles in several rounds, prefetching the next tile's first stages under the current tile's epilogue
-# (hand-counted vmcnt waits: csrc/gemm.hip `stores_behind`).  None of that runs when a launch has fewer tiles than CUs.
+# (hand-counted vmcnt waits: csrc/gemm_nt.hip `stores_behind`).  None of that runs when a launch has fewer tiles than CUs.
 HEADLINE_M = 64 * 1569
 HEADLINE_NK = [(1152, 384), (384, 384), (1536, 384), (384, 1536)]
 

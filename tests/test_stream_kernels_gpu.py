@@ -79,11 +79,11 @@ def ln_bwd_plan(M):
 
 
 DetPlan = namedtuple("DetPlan", "tall vec unrolled remainder nv grid")
-DET_TALL_CG, DET_TALL_PL = 4, 64  # csrc/dcv_common.hpp:250
+DET_TALL_CG, DET_TALL_PL = 4, 64  # csrc/det_reduce.hip
 
 
 def det_reduce_plan(nparts, nA, QA, ldA, nB, part_stride, aligned=True):
-    """csrc/dcv_common.hpp:358-375.  vec: every extent a multiple of 4 and 16-byte aligned pointers; tall: nparts >= 32 and at most 16 384
+    """csrc/det_reduce.hip det_reduce().  vec: every extent a multiple of 4 and 16-byte aligned pointers; tall: nparts >= 32 and at most 16 384
     column groups; unrolled: the 8-loads-in-flight loop runs at least once (flat :219 `k + 8 <= nparts`; tall :266, part lane 0:
     `7 * 64 < nparts`); remainder: some thread then adds parts one at a time (flat :234, tall :281)."""
     vec = aligned and not any(v & 3 for v in (nA, QA, ldA, nB, part_stride))

@@ -1,4 +1,4 @@
-"""What the vendor GEMM (torch.matmul -> hipBLASLt/rocBLAS) reaches on the step's GEMM shapes: a ceiling reference for csrc/gemm.hip."""
+"""What the vendor GEMM (torch.matmul -> hipBLASLt/rocBLAS) reaches on the step's GEMM shapes: a ceiling reference for csrc/gemm_nt.hip and csrc/gemm_tn.hip."""
 import torch, json
 M = 64 * 1569
 def t(fn, n=20):

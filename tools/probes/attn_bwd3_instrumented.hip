@@ -539,16 +539,6 @@ extern "C" int dcv_k3_stamps(void* host_dst, size_t bytes) {
 }
 #endif
 
-static int k3_cus() {
-    static int n = 0;
-    if (!n) {
-        int dev = 0;
-        hipDeviceProp_t p;
-        n = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess && p.multiProcessorCount > 0) ? p.multiProcessorCount : 256;
-    }
-    return n;
-}
-
 // dK / dV of all keys.  The persistent kernel takes the key blocks of 256; a remainder of at most 128 keys per (batch, head) (N = 1569: 33) would
 // cost it a whole item time per pair with one wave of four at work and leave the workgroups unevenly loaded (10.5 items each): that remainder
 // goes to the second form (attn_bwd.hip, 128 keys per workgroup), launched behind it on the same stream for exactly those keys.
@@ -560,7 +550,7 @@ int dcv_dkdv3_launch(const void* qkv, const void* dO, const float* lse, const fl
     a.key_lo = 0;
     a.key_hi = split ? N - rem : N;
     const long items = (long)B * H * ((a.key_hi + K3_KEYS - 1) / K3_KEYS);
-    const int cus = k3_cus();  // one workgroup per CU (149 KB of LDS, > 256 registers per lane)
+    const int cus = dcv_cu_count();  // one workgroup per CU (149 KB of LDS, > 256 registers per lane)
     hipLaunchKernelGGL(attn_bwd_dkdv3p_kernel, dim3((unsigned)(items < cus ? items : cus)), dim3(256), 0, stream, a);
     if (hipGetLastError() != hipSuccess) return DCV_ERR_LAUNCH;
     if (split) return dcv_dkdv2_range(qkv, dO, lse, ws, dqkv, B, N, Nq, H, scale, N - rem, stream);

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Prints registers / LDS / occupancy of every kernel in one csrc file: tools/resource_usage.sh gemm.hip [extra flags]
+# Prints registers / LDS / occupancy of every kernel in one csrc file: tools/resource_usage.sh gemm_nt.hip [extra flags]
 f=$1; shift
 extra=""
 case $f in
