@@ -11,7 +11,8 @@ from .optim import HipAdamW, clip_grad_norm_, param_groups  # noqa: F401
 from .checkpoint import save_checkpoint, load_checkpoint, evaluate, dump_features, eval_subset_channels  # noqa: F401
 from .graph import GraphedTrainStep  # noqa: F401
 from .averaging import AveragedModel  # noqa: F401
+from .augment import DeviceAugment, AugmentParams, tps_coefficients  # noqa: F401
 from .hip import set_deterministic, is_deterministic  # noqa: F401
 
-__all__ = ["DiChaViT", "dichavit", "proxy_loss", "DataParallel", "HipAdamW", "GraphedTrainStep", "AveragedModel", "clip_grad_norm_", "param_groups", "save_checkpoint", "load_checkpoint",
+__all__ = ["DiChaViT", "dichavit", "proxy_loss", "DataParallel", "HipAdamW", "GraphedTrainStep", "AveragedModel", "DeviceAugment", "AugmentParams", "tps_coefficients", "clip_grad_norm_", "param_groups", "save_checkpoint", "load_checkpoint",
            "evaluate", "dump_features", "eval_subset_channels", "set_deterministic", "is_deterministic"]

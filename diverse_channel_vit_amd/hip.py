@@ -69,6 +69,8 @@ _SIGS = {
     "dcv_patch_dgrad": ([_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp], _i),
     "dcv_gather_tokens": ([_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp], _i),
     "dcv_fill_cls": ([_vp, _vp, _vp, _i, _l, _i, _vp], _i),
+    "dcv_tps_warp": ([_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp], _i),
+    "dcv_crop_resize_flip": ([_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp], _i),
     "dcv_ortho_fwd": ([_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp], _i),
     "dcv_ortho_bwd": ([_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp], _i),
     "dcv_proxy_loss_supported": ([_i, _i], _i),
@@ -526,6 +528,67 @@ def gather_tokens(x, idx, out, B, N, Nk, D, scatter=False):
 
 def fill_cls(x, cls, pos0, B, batch_stride, D):
     _check(load().dcv_fill_cls(_p(x), _p(cls), _p(pos0), B, batch_stride, D, _stream()), "dcv_fill_cls")
+
+
+TPS_MIN_W, TPS_MAX_W, TPS_MAX_K, CROP_MAX_SCALE = 21, 1024, 32, 8
+
+
+def _images(x, name):
+    """Shape and dtype of a raw image batch, checked before anything touches the device: (B, C, H, W)."""
+    if x.dim() != 4:
+        raise ValueError(f"{name}: expected images [B, C, H, W], got {tuple(x.shape)}")
+    if x.dtype not in (torch.float32, torch.uint8):
+        raise ValueError(f"{name}: expected float32 or uint8 images, got {x.dtype}")
+    return tuple(x.shape)
+
+
+def tps_warp(x, P, coef, apply, out):
+    """out[b] f32 = the reference's thin-plate-spline warp of x[b] for the samples with apply[b] != 0 (include/dcv.h: dcv_tps_warp); the other
+    samples of out are not written.  x [B, C, W, W] uint8 / float32, P f64 [B, K, 2], coef f64 [B, 2, K + 3], apply int32 [B]."""
+    B, C, H, W = _images(x, "tps_warp: x")
+    if H != W:
+        raise ValueError(f"tps_warp: square images only (the reference's corner points mix width and height otherwise), got {H} x {W}")
+    if not TPS_MIN_W <= W <= TPS_MAX_W:
+        raise ValueError(f"tps_warp: {TPS_MIN_W} <= W <= {TPS_MAX_W}, got {W}")
+    K = P.shape[1] if P.dim() == 3 else 0
+    if not 1 <= K <= TPS_MAX_K or P.shape != (B, K, 2) or coef.shape != (B, 2, K + 3) or apply.shape != (B,) or out.shape != x.shape:
+        raise ValueError(f"tps_warp: P [B, K <= {TPS_MAX_K}, 2], coef [B, 2, K + 3], apply [B], out like x")
+    _req(x, x.dtype, "x"); _req(P, torch.float64, "P"); _req(coef, torch.float64, "coef"); _req(apply, torch.int32, "apply"); _req(out, torch.float32, "out")
+    with _timer(lambda: (f"tps_warp_kernel<{'uint8_t' if x.dtype == torch.uint8 else 'float'}>", f"B{B} C{C} W{W}", 0.0, None,
+                         float(B * C * W * W * (x.element_size() + 4)))):  # all samples flagged
+        rc = load().dcv_tps_warp(_p(x), 1 if x.dtype == torch.uint8 else 0, _p(P), _p(coef), _p(apply), _p(out), B, C, W, K, _stream())
+    _check(rc, "dcv_tps_warp")
+
+
+def check_crop_boxes(box, H, W, S):
+    """box: host int [B, 4] rows (i, j, h, w).  ValueError for a box outside the H x W image or one that shrinks by more than 8 on an axis."""
+    for i, j, h, w in box.tolist():
+        if h < 1 or w < 1 or i < 0 or j < 0 or i + h > H or j + w > W:
+            raise ValueError(f"crop box (i={i}, j={j}, h={h}, w={w}) leaves the {H} x {W} image")
+        if h > CROP_MAX_SCALE * S or w > CROP_MAX_SCALE * S:
+            raise ValueError(f"crop box {h} x {w} -> {S}: scale > {CROP_MAX_SCALE} is not supported")
+
+
+def crop_resize_flip(x, warped, use_warped, box, flip, out):
+    """out f32 [B, C, S, S] = box[b] of (warped[b] if use_warped[b] else x[b]) resized as torch's antialiased bilinear interpolate, mirrored where
+    flip[b] (include/dcv.h: dcv_crop_resize_flip); warped None: all from x.  box int32 [B, 4] ON THE DEVICE: check_crop_boxes() is for its host copy."""
+    B, C, H, W = _images(x, "crop_resize_flip: x")
+    if out.dim() != 4 or out.shape[:2] != (B, C) or out.shape[2] != out.shape[3]:
+        raise ValueError("crop_resize_flip: out [B, C, S, S]")
+    S = out.shape[2]
+    if (warped is not None and (warped.shape != x.shape or use_warped.shape != (B,))) or flip.shape != (B,) or box.shape != (B, 4):
+        raise ValueError("crop_resize_flip: warped like x, use_warped [B], box [B, 4], flip [B]")
+    _req(x, x.dtype, "x"); _req(box, torch.int32, "box")
+    if warped is None:
+        use_warped = None  # every sample is read from x
+    else:
+        _req(warped, torch.float32, "warped"); _req(use_warped, torch.int32, "use_warped")
+    _req(flip, torch.int32, "flip"); _req(out, torch.float32, "out")
+    with _timer(lambda: (f"crop_resize_flip_kernel<{'uint8_t' if x.dtype == torch.uint8 else 'float'}>", f"B{B} C{C} H{H} W{W} S{S}", 0.0, None,
+                         float(B * C * (H * W * x.element_size() + S * S * 4)))):  # whole-image boxes, nothing warped
+        rc = load().dcv_crop_resize_flip(_p(x), 1 if x.dtype == torch.uint8 else 0, _p(warped), _p(use_warped), _p(box), _p(flip), _p(out), B, C, H, W, S,
+                                         _stream())
+    _check(rc, "dcv_crop_resize_flip")
 
 
 def ortho_fwd(Y, S, selfsq, tot, inv_norm, stats, B, Cc, n, D):

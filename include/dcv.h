@@ -260,6 +260,26 @@ int dcv_patch_dgrad(const void* dY, const void* W, const int* ch_idx, const floa
 int dcv_gather_tokens(const float* x, const int* idx, float* out, int B, int N, int Nk, int D, int scatter, void* stream);
 int dcv_fill_cls(float* x, const float* cls, const float* pos0, int B, long batch_stride, int D, void* stream);
 
+/* Train-time augmentation of the CHAMMI recipe on the device (csrc/augment.hip; the reference runs it per image on the host,
+ * datasets/dataset_utils.py:234-243: TPSTransform, RandomResizedCrop(antialias=True), RandomHorizontalFlip).  Two launches, no atomics,
+ * bitwise reproducible.
+ * Thin-plate-spline warp of square images (datasets/tps_transform.py:22-134, its semantics kept: the coarse grid of int((W - 1) / 10)
+ * points per axis evaluated in fp64, the upsampling rule pos = ((W - 1) / 10 - 1) i / (W - 1) — a zero-displacement warp zooms slightly and
+ * clamps at the far edge —, then a bilinear sample with scipy's mode="reflect").  x [B, C, W, W] u8 (x_is_u8) or f32; P f64 [B, K, 2] the
+ * control points (the displaced points followed by the four corners), coef f64 [B, 2, K + 3] per output axis the K kernel weights then
+ * (a1, ax, ay); apply int32 [B]; out f32 [B, C, W, W] in x's units.  Only samples with apply[b] != 0 are written: the others cost no work
+ * and their part of out keeps its contents.  21 <= W <= 1024, K <= 32, B <= 65535, C W W < 2^31, else DCV_ERR_UNSUPPORTED; P, coef 8-byte,
+ * the rest 4-byte aligned.  Whatever P and coef hold, every read stays inside the sample. */
+int dcv_tps_warp(const void* x, int x_is_u8, const double* P, const double* coef, const int* apply, float* out, int B, int C, int W, int K,
+                 void* stream);
+/* out f32 [B, C, S, S] = the box (i, j, h, w) = box[b] (int32 [B, 4]) of sample b resized with torch's interpolate(mode="bilinear",
+ * align_corners=False, antialias=True) rule (fp32 centres and normalised triangle weights over max(n_in / S, 1) pixels per axis), the output
+ * column mirrored where flip[b] != 0.  Sample b is read from warped (f32 [B, C, H, W]) where use_warped[b] != 0, else from x (u8 or f32,
+ * [B, C, H, W]); warped NULL: all from x, use_warped is not read.  A box is cut to the image before use and at most 17 taps per axis are taken (n_in / S <= 8: the caller checks its boxes),
+ * so nothing outside the sample is read whatever the table holds.  B, C <= 65535 and H, W, S <= 32768, else DCV_ERR_UNSUPPORTED. */
+int dcv_crop_resize_flip(const void* x, int x_is_u8, const float* warped, const int* use_warped, const int* box, const int* flip, float* out,
+                         int B, int C, int H, int W, int S, void* stream);
+
 /* ortho_proj_loss_fn_v2 statistics (loss_fn.py:24-48): stats[b] = (pos_sum, neg_sum) of image b.
  * S [B,C,D], selfsq [B,C], tot [B,D], inv_norm [B,C*n] are outputs kept for the backward. */
 int dcv_ortho_fwd(const float* Y, float* S, float* selfsq, float* tot, float* inv_norm, float* stats, int B, int C, int n, int D,
