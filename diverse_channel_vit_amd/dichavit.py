@@ -383,6 +383,20 @@ class ChannelVisionTransformer(_Holder):
         return self._linked_owner("get_attention_rollout")._probe_rollout(x, chunk, training_chunks, new_channel_init, start_layer % depth,
                                                                           float(residual), start)
 
+    def get_attention_relevance(self, x, dfeat, extra_tokens={}, *, chunk="", training_chunks=None, new_channel_init=None, start_layer=0, start=None):
+        """Which patches of which channels speak for one direction of the CLS feature: gradient-weighted attention relevance (Chefer, Gur & Wolf,
+        2021) of the scalar <feature, dfeat>, as one fp32 [B, N] tensor on x's device, detached.  dfeat: fp32 [B, D] on x's device.  See
+        DiChaViT.get_attention_relevance, which also takes class indices; this is the form for an encoder used without a classifier head."""
+        depth = len(self.blocks)
+        if isinstance(start_layer, bool) or not isinstance(start_layer, int) or not -depth <= start_layer < depth:
+            raise ValueError(f"start_layer={start_layer!r}: expected an int in [{-depth}, {depth})")
+        if start is not None and not isinstance(start, torch.Tensor):
+            raise ValueError(f"start: expected None or an fp32 [B, N] tensor, got {type(start).__name__}")
+        if not isinstance(dfeat, torch.Tensor) or dfeat.dtype != torch.float32:
+            raise ValueError("dfeat: expected an fp32 [B, D] tensor (the direction in feature space whose relevance is wanted)")
+        return self._linked_owner("get_attention_relevance")._probe_relevance(x, chunk, training_chunks, new_channel_init, start_layer % depth,
+                                                                            start, dfeat)
+
     @staticmethod
     def _init_weights(m):  # dichavit.py:509-516
         if isinstance(m, nn.Linear):
@@ -1146,13 +1160,15 @@ class DiChaViT(nn.Module):
         hip.ln_fwd(xcur, fe.norm.weight, fe.norm.bias, feat, meanf, rstdf, f.B, f.D, LN_EPS, x_row_stride=row_stride)
         return feat, meanf, rstdf
 
-    def _run_forward(self, x, ch_idx_dev, C, E, pos_tab, want_ortho, save, keep=None, st_scale=None, st_shift=None, tok=None, frozen_k=None):
+    def _run_forward(self, x, ch_idx_dev, C, E, pos_tab, want_ortho, save, keep=None, st_scale=None, st_shift=None, tok=None, frozen_k=None,
+                     refresh=True):
         """The training / eval forward: operand copies, tokeniser, blocks, final norm.  Returns the state: feat, stats and, with save, what the
         backward reads.  frozen_k=k (with save): blocks < k and the tokeniser keep nothing for the backward (they run as with save=False, on
         the same kernels); st["layers"] still has one entry per block — the backward indexes it by block number — which for blocks < k holds
-        the DropPath factors only."""
+        the DropPath factors only.  refresh=False: the operand copies are the caller's business (_probe_relevance)."""
         depth = len(self.feature_extractor.blocks)
-        self._refresh_operand_copies(stochastic=bool(save) and self.training and self.stochastic_weight_rounding, prescale_q=bool(self.attn_prescaled))
+        if refresh:
+            self._refresh_operand_copies(stochastic=bool(save) and self.training and self.stochastic_weight_rounding, prescale_q=bool(self.attn_prescaled))
         f, xcur, stats, kept = self._tokenise(x, ch_idx_dev, C, E, pos_tab, want_ortho, keep, st_scale, st_shift, tok)
         fk = frozen_k if save else None
         st = dict(B=f.B, C=C, n=f.n, N=f.N, M=f.M, save=save, tok=f.tok, ps=f.ps, frozen_k=fk)
@@ -1244,7 +1260,8 @@ class DiChaViT(nn.Module):
         # what the blocks' backwards share; ps: the forward of this pass ran with pre-scaled q: qkv holds q', the backward entries must match
         b = types.SimpleNamespace(B=B, N=N, M=M, g=g, nt_kw=nt_kw, ps=bool(st.get("ps")), sc=sc,
                                   du=torch.empty(Ms, D, dtype=bf, device=dev), dO=torch.empty(Ms, D, dtype=bf, device=dev),
-                                  delta=torch.empty(2, B, H, N if Ms else 0, dtype=f32, device=dev))  # attention backward workspace: -delta, lse*log2e
+                                  delta=torch.empty(2, B, H, N if Ms else 0, dtype=f32, device=dev),  # attention backward workspace: -delta, lse*log2e
+                                  probe=st.get("probe"))  # get_attention_relevance: called with (L, b) once a block's b.dO is written
         for li in range(len(fe.blocks) - 1, k0 - 1, -1):
             blk = fe.blocks[li]
             below = st["layers"][li - 1].get("drop") if li > 0 else None
@@ -1256,6 +1273,8 @@ class DiChaViT(nn.Module):
                 with sc.on_side():
                     dp.grad_ready(ga, *self._range_of([blk.norm1.weight, blk.mlp.fc2.bias]))
         sc.join()
+        if b.probe is not None:  # an inspection call: the walk ends above block k0, no gradient leaves
+            return None, None, []
         if fk is not None:
             return None, None, [self._gview(ga, p) if p.requires_grad else None for p in self._enc_params]
         return self._tokeniser_backward(st, dx, dstats, ga, g, dp)
@@ -1292,12 +1311,16 @@ class DiChaViT(nn.Module):
             if sc.wgrads:
                 hip.gemm_tn_acc(dxb, L["o_c"], g(blk.attn.proj.weight), g(blk.attn.proj.bias))
             b.dO.view(B, N, D)[:, 0].copy_(dO_c)  # only the CLS rows of dO are read (nq = 1)
+            if b.probe is not None:
+                b.probe(L, b)
             hip.attn_bwd(L["qkv"], L["o"], b.dO, L["lse"], b.delta, sc.dqkv, B, N, H, D // H, _ATTN_SCALE, nq=1, prescaled=b.ps)
             dx_c, dx = dx, torch.zeros(M, D, dtype=torch.float32, device=dx.device)  # the residual gradient reaches the block input at the CLS rows only
             dx.view(B, N, D)[:, 0].copy_(dx_c)
             sc.dxb = torch.empty(M, D, dtype=torch.bfloat16, device=dx.device)
         else:
             hip.gemm_nt(dxb, self._bf(blk.attn.proj.weight, True), hip.EPI_PLAIN_BF16, b.dO, **nt_kw)
+            if b.probe is not None:
+                b.probe(L, b)
             sc.wgrad(dxb, L["o"], g(blk.attn.proj.weight), g(blk.attn.proj.bias))
             hip.attn_bwd(L["qkv"], L["o"], b.dO, L["lse"], b.delta, sc.fresh("dqkv"), B, N, H, D // H, _ATTN_SCALE, prescaled=b.ps)
         hip.gemm_nt(sc.dqkv, self._bf(blk.attn.qkv.weight, True), hip.EPI_PLAIN_BF16, b.du, **nt_kw)
@@ -1592,16 +1615,7 @@ class DiChaViT(nn.Module):
             depth = len(self.feature_extractor.blocks)
             B = tk.x.shape[0]
             N = len(tk.keep) if tk.keep is not None else tk.C * tk.n + 1
-            if start is None:
-                r = torch.zeros(B, N, dtype=torch.float32, device=tk.x.device)
-                r[:, 0] = 1.0
-            else:
-                if start.dtype != torch.float32 or tuple(start.shape) != (B, N) or start.device != tk.x.device:
-                    raise ValueError(f"start: expected an fp32 tensor of shape ({B}, {N}) (the tokens this forward sees) on {tk.x.device}, got "
-                                     f"{start.dtype} {tuple(start.shape)} on {start.device}")
-                if not bool((start >= 0).all()):  # one host read: also refuses NaN
-                    raise ValueError("start: every weight must be >= 0")
-                r = start.detach().contiguous().clone()
+            r = self._start_weights(start, B, N, tk.x.device)
             f, xcur = self._inspection_tokenise(tk)
             pre_ln, kept = None, []
             for bi in range(depth):
@@ -1616,6 +1630,96 @@ class DiChaViT(nn.Module):
                 qkv, lse = kept.pop()  # the last block first; a block's qkv is released as soon as its step is queued
                 hip.attn_rollout_step(qkv, lse, r, nxt, f.B, f.N, f.H, f.D // f.H, _ATTN_SCALE, residual, prescaled=f.ps)
                 r, nxt = nxt, r
+            return r
+
+    @staticmethod
+    def _start_weights(start, B, N, device):
+        """The query weights a rollout or relevance walk starts from: one-hot CLS, or a private copy of the caller's checked fp32 [B, N]."""
+        if start is None:
+            r = torch.zeros(B, N, dtype=torch.float32, device=device)
+            r[:, 0] = 1.0
+            return r
+        if start.dtype != torch.float32 or tuple(start.shape) != (B, N) or start.device != device:
+            raise ValueError(f"start: expected an fp32 tensor of shape ({B}, {N}) (the tokens this forward sees) on {device}, got "
+                             f"{start.dtype} {tuple(start.shape)} on {start.device}")
+        if not bool((start >= 0).all()):  # one host read: also refuses NaN
+            raise ValueError("start: every weight must be >= 0")
+        return start.detach().contiguous().clone()
+
+    def get_attention_relevance(self, x, target=None, *, chunk="", training_chunks=None, new_channel_init=None, start_layer=0, start=None):
+        """Which patches of which channels speak for THIS class: gradient-weighted attention relevance (Chefer, Gur & Wolf, 2021, "Generic
+        Attention-model Explainability") with mean head fusion, as one fp32 [B, N] tensor on x's device, detached (an inspection API: the call runs
+        under no_grad from the caller's view; create_graph does not apply).  With L blocks and t the explained scalar,
+            r = start^T (I + A^_{L-1}) (I + A^_{L-2}) ... (I + A^_{start_layer}),     A^_l = mean_h relu(dt / dA_l . A_l)
+        (A_l the softmax attention of block l): the CLS row of the relevance matrix, pushed through the blocks from the last one down — the order
+        in which the backward visits them.  One eval-style forward with activations kept, the data-only backward (no weight-gradient GEMM, no
+        gradient arena, no .grad touched, no collective) and one dcv_attn_relevance_step per block, launched when that block's gradient with
+        respect to its attention output exists; dA = dO V^T is formed inside the kernel and no N x N array is ever written.  The operand copies are
+        private round-to-nearest ones: the call is deterministic and leaves the stochastic rounding seed and a pending training backward alone.
+
+        target: None — the argmax of this call's own logits —, an integer tensor [B] of class indices (t = logit[target]), or an fp32 [B, D]
+        tensor on x's device, a direction in feature space (t = <feature, target>; required when the model has no classifier head: pass the
+        class proxy).  The tokens are prepared as forward() prepares them (chunk, training_chunks, new_channel_init as in get_intermediate_layers;
+        HCS sampling and token drop in train mode: N is the tokens this forward saw); uint8 images go through the input affine.
+        The result is not normalised: r[:, 0] >= 1 is the mass on CLS, token 1 + c * n_p + i = patch i of channel c in this forward's token
+        order, so without token drop r[:, 1:].view(B, C, gh, gw) are the per-channel patch maps.
+        start_layer, start: as in get_attention_rollout (blocks below start_layer launch nothing and the backward stops above them)."""
+        depth = len(self.feature_extractor.blocks)
+        if isinstance(start_layer, bool) or not isinstance(start_layer, int) or not -depth <= start_layer < depth:
+            raise ValueError(f"start_layer={start_layer!r}: expected an int in [{-depth}, {depth})")
+        if start is not None and not isinstance(start, torch.Tensor):
+            raise ValueError(f"start: expected None or an fp32 [B, N] tensor, got {type(start).__name__}")
+        if target is not None and not isinstance(target, torch.Tensor):
+            raise ValueError(f"target: expected None, an integer [B] tensor or an fp32 [B, D] tensor, got {type(target).__name__}")
+        with torch.autocast(device_type="cuda", enabled=False):
+            return self._probe_relevance(x, chunk, training_chunks, new_channel_init, start_layer % depth, start, target)
+
+    def _probe_relevance(self, x, chunk_name, training_chunks, new_channel_init, start_layer, start, target):
+        """get_attention_relevance: the forward of _EncoderFn with the blocks from start_layer up kept, on private round-to-nearest operand copies
+        (straight, transposed and the pre-scaled q bias, swapped in for the duration of the call), then the data-only backward down to block
+        start_layer with a hook that launches dcv_attn_relevance_step on each block's qkv, LSE and dO between two ping-pong [B, N] buffers."""
+        with self._inspection_tokens(x, chunk_name, training_chunks, new_channel_init) as tk:
+            dev, D = tk.x.device, self.dim
+            B = tk.x.shape[0]
+            N = len(tk.keep) if tk.keep is not None else tk.C * tk.n + 1
+            head = self.classifer_head if isinstance(self.classifer_head, nn.Linear) else None
+            classes = None
+            if target is None or not target.is_floating_point():
+                if head is None:
+                    raise ValueError("target: this model has no classifier head; pass an fp32 [B, D] direction in feature space (e.g. the class proxy)")
+                if target is not None:
+                    if target.dtype not in (torch.int64, torch.int32) or tuple(target.shape) != (B,) or target.device != dev:
+                        raise ValueError(f"target: expected int64 or int32 class indices of shape ({B},) on {dev}, got {target.dtype} "
+                                         f"{tuple(target.shape)} on {target.device}")
+                    if not bool(((target >= 0) & (target < head.out_features)).all()):  # one host read
+                        raise ValueError(f"target: every class index must lie in [0, {head.out_features})")
+                    classes = target.long()
+            elif target.dtype != torch.float32 or tuple(target.shape) != (B, D) or target.device != dev:
+                raise ValueError(f"target: expected an fp32 direction of shape ({B}, {D}) on {dev}, got {target.dtype} {tuple(target.shape)} on "
+                                 f"{target.device}")
+            r = self._start_weights(start, B, N, dev)
+            nxt = torch.empty_like(r)
+            H = self.feature_extractor.num_heads
+
+            def step(L, b):
+                nonlocal r, nxt
+                hip.attn_relevance_step(L["qkv"], L["lse"], b.dO, r, nxt, B, N, H, D // H, _ATTN_SCALE, nq=1 if L["tail"] else None, prescaled=b.ps)
+                r, nxt = nxt, r
+
+            own = self._bf16, self._bf16_t, self._qbias
+            self._bf16, self._bf16_t, self._qbias = (torch.empty_like(t) for t in own)
+            try:
+                self._refresh_operand_copies(stochastic=False, prescale_q=bool(self.attn_prescaled))
+                st = self._run_forward(tk.x, tk.ch_idx_dev, tk.C, tk.E_tok, tk.pos_tab, False, save=True, keep=tk.keep, st_scale=tk.scale,
+                                       st_shift=tk.shift, tok=tk.tok, frozen_k=start_layer, refresh=False)
+                if target is None:
+                    classes = head(st["feat"]).argmax(1)
+                dfeat = target if classes is None else head.weight.detach().float()[classes]
+                st.update(data_only=True, probe=step)
+                self._run_backward(st, dfeat.contiguous(), None)
+                st.clear()
+            finally:
+                self._bf16, self._bf16_t, self._qbias = own
             return r
 
     def _ortho_from_stats(self, stats, C, n):

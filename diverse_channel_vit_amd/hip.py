@@ -64,6 +64,8 @@ _SIGS = {
     "dcv_attn_channel_mass_ps": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _l, _vp], _i),
     "dcv_attn_rollout_step": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _vp], _i),
     "dcv_attn_rollout_step_ps": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp], _i),
+    "dcv_attn_relevance_step": ([_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp], _i),
+    "dcv_attn_relevance_step_ps": ([_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp], _i),
     "dcv_im2col_bf16": ([_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp], _i),
     "dcv_patch_bwd": ([_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp], _i),
     "dcv_patch_dgrad": ([_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp], _i),
@@ -485,6 +487,25 @@ def attn_rollout_step(qkv, lse, w, out, B, N, H, hd, scale, alpha, prescaled=Fal
         else:
             rc = load().dcv_attn_rollout_step(_p(qkv), _p(lse), _p(w), _p(out), B, N, H, hd, float(scale), float(alpha), _stream())
     _check(rc, "dcv_attn_rollout_step")
+
+
+def attn_relevance_step(qkv, lse, dO, w, out, B, N, H, hd, scale, nq=None, prescaled=False):
+    """One step of gradient-weighted attention relevance over one block, heads averaged, from qkv, the forward's lse and the gradient dO
+    [B, N, H * hd] bf16 with respect to the attention output (include/dcv.h: dcv_attn_relevance_step):
+    out [B, N] fp32 = w + w^T mean_h relu(dP . P) over the query rows [0, nq) (default: all N), dP = dO V^T, for w [B, N] fp32 >= 0.  out must
+    not overlap w.  prescaled: as attn_probs."""
+    _req(qkv, torch.bfloat16, "qkv"); _req(lse, torch.float32, "lse"); _req(dO, torch.bfloat16, "dO"); _req(w, torch.float32, "w")
+    _req(out, torch.float32, "out")
+    nq_ = N if nq is None else nq
+    if qkv.numel() < B * N * 3 * H * hd or lse.numel() < B * H * N or dO.numel() < B * N * H * hd or w.numel() < B * N or out.numel() < B * N:
+        raise ValueError("attn_relevance_step: qkv holds B*N*3*H*hd elements, lse B*H*N floats, dO B*N*H*hd elements, w and out B*N")
+    with _timer(lambda: (f"attn_relevance_kernel<{'true' if prescaled else 'false'}>", f"B{B} N{N} H{H} Nq{nq_}", 4.0 * B * H * nq_ * N * hd, None,
+                         2.0 * B * (N * 2 + nq_ * 2) * H * hd + 4.0 * B * (nq_ * (H + 1) + 2 * N))):
+        if prescaled:
+            rc = load().dcv_attn_relevance_step_ps(_p(qkv), _p(lse), _p(dO), _p(w), _p(out), B, N, nq_, H, hd, _stream())
+        else:
+            rc = load().dcv_attn_relevance_step(_p(qkv), _p(lse), _p(dO), _p(w), _p(out), B, N, nq_, H, hd, float(scale), _stream())
+    _check(rc, "dcv_attn_relevance_step")
 
 
 def im2col(x, ch_idx, out, B, Ct, C, H, W, P, scale=None, shift=None):

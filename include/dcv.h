@@ -236,6 +236,20 @@ int dcv_attn_rollout_step(const void* qkv, const float* lse, const float* w, flo
                           void* stream);
 int dcv_attn_rollout_step_ps(const void* qkv, const float* lse, const float* w, float* out, int B, int N, int H, int head_dim, float alpha,
                              void* stream);
+/* One step of gradient-weighted attention relevance over one block, heads averaged (ChannelVisionTransformer.get_attention_relevance; Chefer, Gur &
+ * Wolf 2021: R <- R + mean_h relu(grad A . A) R, of which only the CLS row is carried, from the last block down): w, out [B,N] f32, w >= 0,
+ *     out[b,k] = w[b,k] + 1 / H * sum over h and q < Nq of w[b,q] P[b,h,q,k] max(G[b,h,q,k], 0),    P as dcv_attn_probs_rows forms it,
+ *     G[b,h,q,k] = sum_d dO[b,q,h,d] V[b,k,h,d]   (bf16 operands, fp32 accumulation: the dP of the attention backward)
+ * dO [B,N,H*64] bf16 is the gradient with respect to the attention output, 16-byte aligned.  Only the query rows [0, Nq), 1 <= Nq <= N, are read —
+ * from qkv (q part), lse, w and dO; keys and values come from all N rows: nothing a row at or past Nq holds reaches a result (Nq = 1: the CLS-only
+ * last block, whose dO holds its CLS rows alone).  A query with w = 0 contributes exactly nothing, whatever its dO row holds (NaN and Inf
+ * included).  Summed in fp32; no [., N, N] array is written and there is no workspace.  No atomics: the order of every add is fixed by (N, Nq, H) —
+ * bitwise reproducible, and out[b,k] does not depend on the other keys.  Every out[b,k], k < N, is written once and nothing else.  out must not
+ * overlap w: DCV_ERR_UNSUPPORTED.  lse, w, out 4-byte aligned.  The _ps form takes the pre-scaled q of dcv_attn_fwd_rows_ps. */
+int dcv_attn_relevance_step(const void* qkv, const float* lse, const void* dO, const float* w, float* out, int B, int N, int Nq, int H, int head_dim,
+                            float scale, void* stream);
+int dcv_attn_relevance_step_ps(const void* qkv, const float* lse, const void* dO, const float* w, float* out, int B, int N, int Nq, int H,
+                               int head_dim, void* stream);
 
 /* x [B,Ct,H,W] f32 (x_is_u8 == 0: normalised images, the reference's batch format) or u8 (raw pixels), ch_idx int32[C]
  * (device) -> bf16 [B*C*(H/P)*(W/P), P*P] patch rows (dichavit.py:134/210,377).  scale/shift f32[C] (nullable, indexed by
