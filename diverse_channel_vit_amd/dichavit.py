@@ -190,6 +190,17 @@ def _parse_layers(n, depth: int) -> List[int]:
     return blocks
 
 
+def _parse_walk(depth: int, start_layer, start, residual=0.5) -> int:
+    """The arguments the rollout and relevance calls share (residual: the rollout's alone) -> the first block walked; ValueError before any device work."""
+    if isinstance(start_layer, bool) or not isinstance(start_layer, int) or not -depth <= start_layer < depth:
+        raise ValueError(f"start_layer={start_layer!r}: expected an int in [{-depth}, {depth})")
+    if isinstance(residual, bool) or not isinstance(residual, (int, float)) or not 0.0 <= residual < 1.0:
+        raise ValueError(f"residual={residual!r}: expected a number in [0, 1)")
+    if start is not None and not isinstance(start, torch.Tensor):
+        raise ValueError(f"start: expected None or an fp32 [B, N] tensor, got {type(start).__name__}")
+    return start_layer % depth
+
+
 class _Holder(nn.Module):
     def forward(self, *a, **k):  # pragma: no cover
         raise RuntimeError("parameter container of the HIP path; call DiChaViT.forward")
@@ -373,29 +384,17 @@ class ChannelVisionTransformer(_Holder):
         residual: in [0, 1): the weight of the identity (the residual connection) in every block; 0.5 with start_layer=0 is the paper's rollout.
         start: None — one-hot CLS — or an fp32 [B, N] tensor on x's device, >= 0 (checked with one host read): the query weights to roll.
         Memory: the qkv and LSE of the rolled blocks are kept until the walk down (231 MB per block at B 64, 8 channels, 224 x 224, ViT-S)."""
-        depth = len(self.blocks)
-        if isinstance(start_layer, bool) or not isinstance(start_layer, int) or not -depth <= start_layer < depth:
-            raise ValueError(f"start_layer={start_layer!r}: expected an int in [{-depth}, {depth})")
-        if isinstance(residual, bool) or not isinstance(residual, (int, float)) or not 0.0 <= residual < 1.0:
-            raise ValueError(f"residual={residual!r}: expected a number in [0, 1)")
-        if start is not None and not isinstance(start, torch.Tensor):
-            raise ValueError(f"start: expected None or an fp32 [B, N] tensor, got {type(start).__name__}")
-        return self._linked_owner("get_attention_rollout")._probe_rollout(x, chunk, training_chunks, new_channel_init, start_layer % depth,
-                                                                          float(residual), start)
+        first = _parse_walk(len(self.blocks), start_layer, start, residual)
+        return self._linked_owner("get_attention_rollout")._probe_rollout(x, chunk, training_chunks, new_channel_init, first, float(residual), start)
 
     def get_attention_relevance(self, x, dfeat, extra_tokens={}, *, chunk="", training_chunks=None, new_channel_init=None, start_layer=0, start=None):
         """Which patches of which channels speak for one direction of the CLS feature: gradient-weighted attention relevance (Chefer, Gur & Wolf,
         2021) of the scalar <feature, dfeat>, as one fp32 [B, N] tensor on x's device, detached.  dfeat: fp32 [B, D] on x's device.  See
         DiChaViT.get_attention_relevance, which also takes class indices; this is the form for an encoder used without a classifier head."""
-        depth = len(self.blocks)
-        if isinstance(start_layer, bool) or not isinstance(start_layer, int) or not -depth <= start_layer < depth:
-            raise ValueError(f"start_layer={start_layer!r}: expected an int in [{-depth}, {depth})")
-        if start is not None and not isinstance(start, torch.Tensor):
-            raise ValueError(f"start: expected None or an fp32 [B, N] tensor, got {type(start).__name__}")
+        first = _parse_walk(len(self.blocks), start_layer, start)
         if not isinstance(dfeat, torch.Tensor) or dfeat.dtype != torch.float32:
             raise ValueError("dfeat: expected an fp32 [B, D] tensor (the direction in feature space whose relevance is wanted)")
-        return self._linked_owner("get_attention_relevance")._probe_relevance(x, chunk, training_chunks, new_channel_init, start_layer % depth,
-                                                                            start, dfeat)
+        return self._linked_owner("get_attention_relevance")._probe_relevance(x, chunk, training_chunks, new_channel_init, first, start, dfeat)
 
     @staticmethod
     def _init_weights(m):  # dichavit.py:509-516
@@ -1535,6 +1534,11 @@ class DiChaViT(nn.Module):
         f, xcur, _, _ = self._tokenise(tk.x, tk.ch_idx_dev, tk.C, tk.E_tok, tk.pos_tab, False, tk.keep, tk.scale, tk.shift, tk.tok, wbuf, qbias)
         return f, xcur
 
+    @staticmethod
+    def _token_count(tk):
+        """N of the forward that tk prepares, known before its tokeniser runs: the kept tokens under token drop, else CLS + C channels of n patches."""
+        return len(tk.keep) if tk.keep is not None else tk.C * tk.n + 1
+
     def _probe_attention(self, x, chunk_name, layer_idx, query_rows):
         """ChannelVisionTransformer.get_last_selfattention: blocks < layer run as the forward runs them; the probed block stops after its
         norm1, qkv GEMM and the attention of its query rows (for their LSE), from which dcv_attn_probs_rows writes the probabilities
@@ -1544,7 +1548,7 @@ class DiChaViT(nn.Module):
             layer_idx = int(layer_idx)
             if not -depth <= layer_idx < depth:
                 return None
-            N = len(tk.keep) if tk.keep is not None else tk.C * tk.n + 1
+            N = self._token_count(tk)
             rows = N if query_rows is None else int(query_rows)
             if not 1 <= rows <= N:
                 raise ValueError(f"query_rows={query_rows}: expected 1 <= query_rows <= {N} (the tokens this block sees)")
@@ -1614,7 +1618,7 @@ class DiChaViT(nn.Module):
         with self._inspection_tokens(x, chunk_name, training_chunks, new_channel_init) as tk:
             depth = len(self.feature_extractor.blocks)
             B = tk.x.shape[0]
-            N = len(tk.keep) if tk.keep is not None else tk.C * tk.n + 1
+            N = self._token_count(tk)
             r = self._start_weights(start, B, N, tk.x.device)
             f, xcur = self._inspection_tokenise(tk)
             pre_ln, kept = None, []
@@ -1664,15 +1668,11 @@ class DiChaViT(nn.Module):
         The result is not normalised: r[:, 0] >= 1 is the mass on CLS, token 1 + c * n_p + i = patch i of channel c in this forward's token
         order, so without token drop r[:, 1:].view(B, C, gh, gw) are the per-channel patch maps.
         start_layer, start: as in get_attention_rollout (blocks below start_layer launch nothing and the backward stops above them)."""
-        depth = len(self.feature_extractor.blocks)
-        if isinstance(start_layer, bool) or not isinstance(start_layer, int) or not -depth <= start_layer < depth:
-            raise ValueError(f"start_layer={start_layer!r}: expected an int in [{-depth}, {depth})")
-        if start is not None and not isinstance(start, torch.Tensor):
-            raise ValueError(f"start: expected None or an fp32 [B, N] tensor, got {type(start).__name__}")
+        first = _parse_walk(len(self.feature_extractor.blocks), start_layer, start)
         if target is not None and not isinstance(target, torch.Tensor):
             raise ValueError(f"target: expected None, an integer [B] tensor or an fp32 [B, D] tensor, got {type(target).__name__}")
         with torch.autocast(device_type="cuda", enabled=False):
-            return self._probe_relevance(x, chunk, training_chunks, new_channel_init, start_layer % depth, start, target)
+            return self._probe_relevance(x, chunk, training_chunks, new_channel_init, first, start, target)
 
     def _probe_relevance(self, x, chunk_name, training_chunks, new_channel_init, start_layer, start, target):
         """get_attention_relevance: the forward of _EncoderFn with the blocks from start_layer up kept, on private round-to-nearest operand copies
@@ -1681,7 +1681,7 @@ class DiChaViT(nn.Module):
         with self._inspection_tokens(x, chunk_name, training_chunks, new_channel_init) as tk:
             dev, D = tk.x.device, self.dim
             B = tk.x.shape[0]
-            N = len(tk.keep) if tk.keep is not None else tk.C * tk.n + 1
+            N = self._token_count(tk)
             head = self.classifer_head if isinstance(self.classifer_head, nn.Linear) else None
             classes = None
             if target is None or not target.is_floating_point():

@@ -480,7 +480,7 @@ def attn_rollout_step(qkv, lse, w, out, B, N, H, hd, scale, alpha, prescaled=Fal
     _req(qkv, torch.bfloat16, "qkv"); _req(lse, torch.float32, "lse"); _req(w, torch.float32, "w"); _req(out, torch.float32, "out")
     if qkv.numel() < B * N * 3 * H * hd or lse.numel() < B * H * N or w.numel() < B * N or out.numel() < B * N:
         raise ValueError("attn_rollout_step: qkv holds B*N*3*H*hd elements, lse B*H*N floats, w and out B*N")
-    with _timer(lambda: (f"attn_rollout_kernel<{'true' if prescaled else 'false'}>", f"B{B} N{N} H{H}", 2.0 * B * H * N * N * hd, None,
+    with _timer(lambda: (f"attn_keysweep_kernel<{'true' if prescaled else 'false'}, false>", f"B{B} N{N} H{H}", 2.0 * B * H * N * N * hd, None,
                          2.0 * B * N * 2 * H * hd + 4.0 * B * N * (H + 2))):
         if prescaled:
             rc = load().dcv_attn_rollout_step_ps(_p(qkv), _p(lse), _p(w), _p(out), B, N, H, hd, float(alpha), _stream())
@@ -499,7 +499,7 @@ def attn_relevance_step(qkv, lse, dO, w, out, B, N, H, hd, scale, nq=None, presc
     nq_ = N if nq is None else nq
     if qkv.numel() < B * N * 3 * H * hd or lse.numel() < B * H * N or dO.numel() < B * N * H * hd or w.numel() < B * N or out.numel() < B * N:
         raise ValueError("attn_relevance_step: qkv holds B*N*3*H*hd elements, lse B*H*N floats, dO B*N*H*hd elements, w and out B*N")
-    with _timer(lambda: (f"attn_relevance_kernel<{'true' if prescaled else 'false'}>", f"B{B} N{N} H{H} Nq{nq_}", 4.0 * B * H * nq_ * N * hd, None,
+    with _timer(lambda: (f"attn_keysweep_kernel<{'true' if prescaled else 'false'}, true>", f"B{B} N{N} H{H} Nq{nq_}", 4.0 * B * H * nq_ * N * hd, None,
                          2.0 * B * (N * 2 + nq_ * 2) * H * hd + 4.0 * B * (nq_ * (H + 1) + 2 * N))):
         if prescaled:
             rc = load().dcv_attn_relevance_step_ps(_p(qkv), _p(lse), _p(dO), _p(w), _p(out), B, N, nq_, H, hd, _stream())

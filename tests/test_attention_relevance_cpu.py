@@ -116,4 +116,4 @@ def test_the_new_symbols_are_declared_and_exported():
         m = re.search(r"\bint " + name + r"\(([^)]*)\);", hdr)
         assert m and len(m.group(1).split(",")) == nargs
     assert callable(hip.attn_relevance_step)
-    assert os.path.exists(os.path.join(ROOT, "diverse_channel_vit_amd", "csrc", "attn_relevance.hip"))
+    assert os.path.exists(os.path.join(ROOT, "diverse_channel_vit_amd", "csrc", "attn_rollout.hip"))  # attn_keysweep_kernel<PS, GRAD = true>

@@ -284,6 +284,31 @@ def test_kernel_structure(hip, prescaled):
     assert bool((big == 0.25).all()) and bool((sink == 0.25).all()) and torch.equal(w, w0)
 
 
+@pytest.mark.parametrize("prescaled", [False, True], ids=["plain", "ps"])
+@pytest.mark.parametrize("B,H,N", [(2, 3, 197), (1, 2, 65), (1, 6, 129)])
+def test_unit_gradients_give_the_rollout_step_bit_for_bit(hip, B, H, N, prescaled):
+    """dO[b, q, h, 0] = 1 and V[b, k, h, 0] = 1, every other dO element 0: G = dO V^T is exactly 1 for every (q, k), so each relevance term
+    p max(G, 0) is p itself, and a row of weight 0 adds the +0 that the rollout's exp2(-inf) adds.  Both steps then form the same tot in the
+    same order, and with the rollout's alpha = 0 both store fl(fl(1 / H) tot) at a key whose own weight is 0.  Two weight vectors, zero on the
+    odd and on the even tokens, cover every key.  (2, 3, 197): four query tiles, two key workgroups, a ragged tail; (1, 2, 65): a second tile of
+    one row, an idle wave, the skipped second query block; (1, 6, 129): the second key workgroup owns a single key."""
+    qkv, _ = _operands(B, N, H, seed=N + H, prescaled=prescaled)
+    lse = _lse(hip, qkv, B, N, H, prescaled)  # of q and k alone
+    qkv.view(B, N, 3, H, 64)[:, :, 2, :, 0] = 1
+    dO = torch.zeros(B, N, H, 64, dtype=torch.bfloat16, device="cuda")
+    dO[..., 0] = 1
+    dO = dO.view(B, N, H * 64)
+    dense = (torch.rand(B, N, generator=torch.Generator(device="cpu").manual_seed(N)) + 1e-3).cuda()
+    odd = (torch.arange(N, device="cuda") % 2 == 1)
+    for dead in (odd, ~odd):
+        w = torch.where(dead, torch.zeros_like(dense), dense)
+        rel = _step(hip, qkv, lse, dO, w, B, N, H, N, prescaled)
+        roll = torch.empty(B, N, device="cuda")
+        hip.attn_rollout_step(qkv, lse, w, roll, B, N, H, 64, SCALE, 0.0, prescaled=prescaled)
+        assert bool((roll[:, dead] > 0).all())  # the live rows reach every key: the comparison is of sums, not of zeros
+        assert torch.equal(rel[:, dead], roll[:, dead])
+
+
 # ------------------------------------------------------------------------------------------------------------------------------------
 # the model
 # ------------------------------------------------------------------------------------------------------------------------------------

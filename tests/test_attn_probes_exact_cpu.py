@@ -23,10 +23,10 @@ Rules (rule()).  Expectation zero: |got| <= DUST = 2^-30.  Elsewhere |got - ref|
 for A, the number of contributing (weight > 0) rows for out.  NaN always fails.  Where 2^-10 comes from, in log2 units of the exponent of exp2, which is formed
 at magnitude about 1110 where an fp32 ulp is 2^-13:
   * the float32 LSE given to the kernel: half an ulp of 768 nats = 2^-15 nats = 4.4e-5 log2 units;
-  * rowc = fl(-lse LOG2E) (attn_probs.hip:63, attn_channel_mass.hip:69, attn_rollout.hip:89): half an ulp of 1108 = 2^-14 = 6.1e-5;
+  * rowc = fl(-lse LOG2E) (attn_probs.hip:63, attn_channel_mass.hip:69, attn_keysweep_kernel's sC row constant): half an ulp of 1108 = 2^-14 = 6.1e-5;
   * the fp32 constants LOG2E and c = scale LOG2E (attn_probs.hip:105): each at most 2^-24 relative of about 1108, 1.3e-4 between them;
-  * the rollout's c_q = fl(log2f(w) - lse LOG2E) (attn_rollout.hip:89): where the product is not contracted into the subtraction, half an ulp more, 6.1e-5;
-  * plain form, exp2(fma(s, c, rowc)) (attn_probs.hip:89, attn_channel_mass.hip:103, attn_rollout.hip:110): one rounding of a difference of magnitude <= 2, nothing;
+  * the rollout's c_q = fl(log2f(w) - lse LOG2E) (attn_keysweep_kernel's sC row constant): where the product is not contracted into the subtraction, half an ulp more, 6.1e-5;
+  * plain form, exp2(fma(s, c, rowc)) (attn_probs.hip:89, attn_channel_mass.hip:103, attn_keysweep_kernel's exp2(fma(...)) line): one rounding of a difference of magnitude <= 2, nothing;
     in all 3.1e-4 log2 units = 2.1e-4 relative on p;
   * pre-scaled form, the accumulator starts at rowc = -1110 - log2 g and takes up to twelve products of +-92.5 (the MFMA's order of accumulation is not
     specified): each partial sum has magnitude <= 1112 and rounds by at most 2^-14: 12 x 6.1e-5 = 7.3e-4 on top of the first three terms less the constant c,
@@ -322,7 +322,7 @@ def probs_plan(N, Nq=None):
 
 
 def rollout_plan(N):
-    """attn_rollout.hip:52-59, 96: key workgroups per image, query tiles, clamped query rows of the last tile, idle waves, the skipped second query block."""
+    """attn_keysweep_kernel (attn_rollout.hip), its nkt, nt, k0 / active and the break of the qb loop: key workgroups per image, query tiles, clamped query rows of the last tile, idle waves, the skipped second query block."""
     nkt, nt = -(-N // 128), -(-N // 64)
     idle = sum(1 for wv in range(4) if (nkt - 1) * 128 + wv * 32 >= N)
     return dict(nkt=nkt, nt=nt, clamped=nt * 64 - N, idle_waves=idle, second_block_skipped=0 < N % 64 <= 32, key_tail=N % 32)
