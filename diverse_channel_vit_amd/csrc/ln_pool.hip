@@ -29,35 +29,13 @@
 // copy floor has not been profiled.
 #include "dcv_common.hpp"
 #include "../../include/dcv.h"
+#include "ln_pool_plan.hpp"  // lp_plan, lp_shape_ok and their constants: shared with ln_pool_bwd.hip
 
 namespace {
 
-constexpr int LP_MAXV_MAX = 4;       // float4 per lane: D <= 64 * 4 * 4 = 1024; instantiated for 2 (D <= 512) and 4, as ln_fwd_kernel
-#ifndef DCV_LP_TARGET_WGS
-#define DCV_LP_TARGET_WGS 2048  // variant builds (tools/intermediate_layers_bench.py --variants): 512 = one workgroup per segment at the headline shape
-#endif
 #ifndef DCV_LP_TWO_ROWS
 #define DCV_LP_TWO_ROWS 0  // 1 (variant builds): two rows' loads in flight per wave; measured no faster (header), as in ln_fwd_kernel
 #endif
-constexpr long LP_TARGET_WGS = DCV_LP_TARGET_WGS;  // workgroups asked for: 8 x 4 waves per CU of a 256-CU chip at 2048
-constexpr int LP_MIN_ROWS = 8;                     // rows per split at least (two per wave)
-
-struct LpPlan {
-    int S;  // splits per segment
-    int R;  // rows per split (the last one may hold fewer)
-};
-
-inline LpPlan lp_plan(int B, int C, int n_p) {
-    const long segs = (long)B * C;
-    long s0 = (LP_TARGET_WGS + segs - 1) / segs;
-    const long cap = n_p / LP_MIN_ROWS > 1 ? n_p / LP_MIN_ROWS : 1;
-    if (s0 > cap) s0 = cap;
-    if (s0 < 1) s0 = 1;
-    LpPlan p;
-    p.R = (int)((n_p + s0 - 1) / s0);
-    p.S = (n_p + p.R - 1) / p.R;
-    return p;
-}
 
 // Workgroups [0, B C S): one (segment, split) each.  Workgroups from B C S on: four CLS rows each (one per wave).
 template <int MAXV>
@@ -206,13 +184,6 @@ __global__ __launch_bounds__(256) void ln_pool_finish_kernel(const float* __rest
     const float4 bb = reinterpret_cast<const float4*>(beta)[c];
     reinterpret_cast<f32x4*>(out + ((size_t)b * (1 + C) + 1 + ch) * D)[c] =
         f32x4{s.x * inv * g.x + bb.x, s.y * inv * g.y + bb.y, s.z * inv * g.z + bb.z, s.w * inv * g.w + bb.w};
-}
-
-inline bool lp_shape_ok(int B, int C, int n_p, int D) {
-    if (B <= 0 || C <= 0 || n_p <= 0 || D <= 0 || (D & 3) || D > 64 * 4 * LP_MAXV_MAX) return false;
-    // grid and index arithmetic stay inside int: segments, workgroups and the rows of one image
-    if ((long)B * C > (1L << 24) || (long)C * n_p > (1L << 28)) return false;
-    return true;
 }
 
 }  // namespace

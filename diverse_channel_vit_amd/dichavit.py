@@ -433,15 +433,22 @@ class _EncoderFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, model, ch_idx_dev, C, want_ortho, keep, tok, x, E, pos_tab, *params):
-        need = ctx.needs_input_grad
+        return _EncoderFn._forward(ctx, ctx.needs_input_grad, None, model, ch_idx_dev, C, want_ortho, keep, tok, x, E, pos_tab)
+
+    @staticmethod
+    def backward(ctx, dfeat, dstats):
+        return _EncoderFn._backward(ctx, dfeat, dstats)
+
+    @staticmethod
+    def _forward(ctx, need, taps, model, ch_idx_dev, C, want_ortho, keep, tok, x, E, pos_tab):
+        """need: needs_input_grad as _EncoderFn.forward's arguments are numbered.  taps: None, or (blocks, pool) of _EncoderTapsFn."""
         # frozen prefix: nothing upstream of the first block k with a trainable parameter needs a gradient — not x, E, the positional table,
         # cls_token or the patch projection (need[6:12]), and by k's definition no parameter of a block below it (12 per block from need[12])
-        frozen_k = None
-        if any(need[12:]) and not any(need[6:12]) and model._dp is None:
-            depth = len(model.feature_extractor.blocks)
-            frozen_k = next((bi for bi in range(depth) if any(need[12 + 12 * bi:24 + 12 * bi])), depth)
+        depth = len(model.feature_extractor.blocks)
+        frozen_k = _frozen_prefix(any(need[6:12]), [any(need[12 + 12 * bi:24 + 12 * bi]) for bi in range(depth)], any(need[12 + 12 * depth:]), model._dp)
         st = model._run_forward(x, ch_idx_dev, C, E, pos_tab, want_ortho, save=any(need), keep=keep,
-                                st_scale=model._cur_scale, st_shift=model._cur_shift, tok=tok, **({} if frozen_k is None else dict(frozen_k=frozen_k)))
+                                st_scale=model._cur_scale, st_shift=model._cur_shift, tok=tok, **({} if frozen_k is None else dict(frozen_k=frozen_k)),
+                                **({} if taps is None else dict(taps=taps)))
         if need[6]:  # dcv_patch_dgrad's operands: the bf16 projection copy this forward multiplied by, the channel index, the input affine's scale
             fe = model.feature_extractor
             P = fe.patch_size
@@ -455,7 +462,7 @@ class _EncoderFn(torch.autograd.Function):
         return st["feat"], st["stats"]
 
     @staticmethod
-    def backward(ctx, dfeat, dstats):
+    def _backward(ctx, dfeat, dstats):
         model, st = ctx.model, ctx.st
         if torch.is_grad_enabled():
             raise RuntimeError("the HIP encoder node has a hand-written first-order backward: create_graph=True (second-order gradients) "
@@ -468,6 +475,41 @@ class _EncoderFn(torch.autograd.Function):
         st["consumed"] = True
         st.clear()
         return (None, None, None, None, None, None, dx, dE, dpos) + tuple(grads)
+
+
+class _EncoderTapsFn(_EncoderFn):
+    """_EncoderFn with feature taps (DiChaViT.forward_with_features): `taps` = (blocks, pool) comes first, then _EncoderFn's arguments; the taps
+    follow feat and stats as extra outputs, and backward takes their gradients.  One that receives none arrives as None (the node does not
+    materialise missing gradients) and launches nothing; with no gradient into feat either — a loss on the taps alone — dfeat is zero."""
+
+    @staticmethod
+    def forward(ctx, taps, model, ch_idx_dev, C, want_ortho, keep, tok, x, E, pos_tab, *params):
+        feat, stats = _EncoderFn._forward(ctx, ctx.needs_input_grad[1:], taps, model, ch_idx_dev, C, want_ortho, keep, tok, x, E, pos_tab)
+        ctx.set_materialize_grads(False)
+        return (feat, stats) + tuple(ctx.st.pop("tap_out"))
+
+    @staticmethod
+    def backward(ctx, dfeat, dstats, *dtaps):
+        st = ctx.st
+        if dfeat is None:
+            dfeat = torch.zeros_like(st["feat"])
+        st["dtaps"] = {l: d for l, d in zip(st["tap_blocks"], dtaps) if d is not None}
+        return (None,) + _EncoderFn._backward(ctx, dfeat, dstats)
+
+
+def _frozen_prefix(upstream: bool, blocks, norm: bool, dp) -> Optional[int]:
+    """The frozen prefix of a forward: the first block with a trainable parameter (len(blocks) when only the final norm has one) when nothing
+    upstream of the blocks needs a gradient and no DataParallel reducer is attached; None when there is no prefix.  blocks: per block, does
+    any of its parameters need a gradient.  The one rule behind _EncoderFn (from needs_input_grad) and forward_with_features' host check."""
+    if dp is not None or upstream or not (any(blocks) or norm):
+        return None
+    return next((bi for bi, b in enumerate(blocks) if b), len(blocks))
+
+
+def _check_taps_above_prefix(tap_blocks, fk) -> None:
+    if fk is not None and tap_blocks and tap_blocks[0] < fk - 1:
+        raise ValueError(f"forward_with_features: block {tap_blocks[0]} lies below the frozen prefix (blocks < {fk}): no trainable block could "
+                         "receive its gradient; get_intermediate_layers returns that feature")
 
 
 class _LinearStatsLossFn(torch.autograd.Function):
@@ -1159,12 +1201,47 @@ class DiChaViT(nn.Module):
         hip.ln_fwd(xcur, fe.norm.weight, fe.norm.bias, feat, meanf, rstdf, f.B, f.D, LN_EPS, x_row_stride=row_stride)
         return feat, meanf, rstdf
 
+    def _tap_forward(self, f, xcur, pool, compact, save):
+        """One feature tap (forward_with_features): the final norm of the stream `xcur` pooled as asked — "channel": [B, 1 + C, D]
+        (dcv_ln_pool_channels), "cls": [B, D], None: [B, N, D] (dcv_ln_fwd, fp32 output).  compact: xcur holds the CLS rows only (the CLS-only
+        tail's output).  Returns (the tap, the row statistics its dcv_ln_bwd reads or None)."""
+        fe, f32 = self.feature_extractor, torch.float32
+        if pool == "channel":
+            cap = torch.empty(f.B, 1 + f.C, f.D, dtype=f32, device=f.dev)
+            hip.ln_pool_channels(xcur, fe.norm.weight, fe.norm.bias, cap, f.B, f.C, f.n, f.D, LN_EPS)
+            return cap, None
+        rows = f.B if pool == "cls" else f.M
+        cap = torch.empty((f.B, f.D) if pool == "cls" else (f.B, f.N, f.D), dtype=f32, device=f.dev)
+        stats = (torch.empty(rows, dtype=f32, device=f.dev), torch.empty(rows, dtype=f32, device=f.dev)) if save else (None, None)
+        hip.ln_fwd(xcur, fe.norm.weight, fe.norm.bias, cap, stats[0], stats[1], rows, f.D, LN_EPS,
+                   **(dict(x_row_stride=f.D if compact else f.N * f.D) if pool == "cls" else {}))
+        return cap, (stats if save else None)
+
+    def _tap_backward(self, tp, l, dtap, dx, g, B, N, compact=False):
+        """The gradient `dtap` of the tap at block l added to dx, the fp32 gradient of the stream after that block, and to the final norm's
+        dgamma / dbeta slots.  compact: the stream is the CLS-only tail's output, dx is [B, D] (pool="cls" at the last block)."""
+        fe, D = self.feature_extractor, self.dim
+        x, stats, pool = tp["x"].pop(l), tp["stats"].pop(l), tp["pool"]
+        gw, gb = g(fe.norm.weight), g(fe.norm.bias)
+        dtap = dtap.contiguous()
+        if pool == "channel":
+            hip.ln_pool_channels_bwd(x, fe.norm.weight, dtap, dx, gw, gb, B, tp["C"], tp["n"], D, LN_EPS)
+        elif pool == "cls":
+            s = D if compact else N * D
+            hip.ln_bwd(dtap, x, stats[0], stats[1], fe.norm.weight, dx, dx, None, gw, gb, B, D, x_row_stride=s, dx_row_stride=s)
+        else:
+            hip.ln_bwd(dtap.view(B * N, D), x, stats[0], stats[1], fe.norm.weight, dx, dx, None, gw, gb, B * N, D)
+
     def _run_forward(self, x, ch_idx_dev, C, E, pos_tab, want_ortho, save, keep=None, st_scale=None, st_shift=None, tok=None, frozen_k=None,
-                     refresh=True):
+                     refresh=True, taps=None):
         """The training / eval forward: operand copies, tokeniser, blocks, final norm.  Returns the state: feat, stats and, with save, what the
         backward reads.  frozen_k=k (with save): blocks < k and the tokeniser keep nothing for the backward (they run as with save=False, on
         the same kernels); st["layers"] still has one entry per block — the backward indexes it by block number — which for blocks < k holds
-        the DropPath factors only.  refresh=False: the operand copies are the caller's business (_probe_relevance)."""
+        the DropPath factors only.  refresh=False: the operand copies are the caller's business (_probe_relevance).
+        taps=(blocks, pool) (forward_with_features): st["tap_out"] lists the final norm of the stream after each listed block, launched right
+        after that block; the last block leaves its CLS-only form when it is tapped with a pool other than "cls".  With save, st["taps"] keeps
+        what their backward reads: the streams themselves — block l + 1's saved x_in, x_final for the last block: no copy — and the row
+        statistics of the pools that go through dcv_ln_bwd."""
         depth = len(self.feature_extractor.blocks)
         if refresh:
             self._refresh_operand_copies(stochastic=bool(save) and self.training and self.stochastic_weight_rounding, prescale_q=bool(self.attn_prescaled))
@@ -1174,16 +1251,29 @@ class DiChaViT(nn.Module):
         if save and fk is None:
             st.update(kept)
         layers, pre_ln = [], None
+        tap_blocks, tap_pool = taps if taps is not None else ((), None)
+        _check_taps_above_prefix(tap_blocks, fk)  # fk from needs_input_grad: the host check of forward_with_features saw requires_grad flags only
+        full_last = bool(tap_blocks) and tap_blocks[-1] == depth - 1 and tap_pool != "cls"  # the last block's rows are all read: no CLS-only tail
+        tap_out, tp = [], dict(pool=tap_pool, C=C, n=f.n, x={}, stats={})
         for bi in range(depth):
             sv = save and (fk is None or bi >= fk)  # this block's activations are kept for the backward
-            tail = self.cls_only_tail and bi == depth - 1  # last block on the CLS rows only: it hands over compact CLS rows
+            tail = self.cls_only_tail and bi == depth - 1 and not full_last  # last block on the CLS rows only: it hands over compact CLS rows
             xcur, pre_ln, L = self._block_forward(f, bi, xcur, pre_ln, sv, tail)
             layers.append(L)
+            if bi in tap_blocks:
+                cap, tstats = self._tap_forward(f, xcur, tap_pool, tail, save)
+                tap_out.append(cap)
+                if save:
+                    tp["x"][bi], tp["stats"][bi] = xcur, tstats
         final_stride = f.D if tail else f.N * f.D
         feat, meanf, rstdf = self._final_norm(f, xcur, final_stride)
         st.update(feat=feat, stats=stats)
+        if taps is not None:
+            st.update(tap_out=tap_out, tap_blocks=tuple(tap_blocks))
         if save:
             st.update(layers=layers, x_final=xcur, final_stride=final_stride, meanf=meanf, rstdf=rstdf, want_ortho=want_ortho)
+            if taps is not None:
+                st["taps"] = tp
         return st
 
     def _gview(self, ga, p):
@@ -1237,6 +1327,15 @@ class DiChaViT(nn.Module):
         dx = torch.zeros(B if fs == D else M, D, dtype=f32, device=dev)
         hip.ln_bwd(dfeat, st["x_final"], st["meanf"], st["rstdf"], fe.norm.weight, None, dx, None, g(fe.norm.weight), g(fe.norm.bias),
                    B, D, x_row_stride=fs, dx_row_stride=fs)
+        # feature taps (forward_with_features): the gradient of the tap at block l joins the fp32 gradient of the stream after block l — for the
+        # last block here, before the bf16 copy is made; for an inner block inside block l + 1's backward (_block_backward).  A tap without a
+        # gradient launches nothing.
+        tp, dtaps = st.get("taps"), st.get("dtaps") or {}
+        last = len(fe.blocks) - 1
+        if last in dtaps:
+            self._tap_backward(tp, last, dtaps.pop(last), dx, g, B, N, compact=fs == D)
+        # data parallel: the final norm's bucket is handed over once the lowest tap's backward has added to it (without taps: here, as ever)
+        norm_after = min(dtaps) + 1 if dtaps else None
         dxb = torch.empty_like(dx, dtype=bf)
         # DropPath (vit.py:37-56): the gradient that enters a residual branch is the stream's gradient times that branch's per-sample
         # factor.  The bf16 copy `dxb` is what the branch's backward reads (input gradient and weight gradient), so the factor goes into
@@ -1248,7 +1347,7 @@ class DiChaViT(nn.Module):
             dxb.copy_((dx.view(B, rows, D) * top[1].view(B, 1, 1)).view_as(dx))
         else:
             hip.cast_bf16(dx, dxb, dx.numel())
-        if dp is not None:
+        if dp is not None and norm_after is None:
             dp.grad_ready(ga, *self._range_of([fe.norm.weight, fe.norm.bias]))
         fk = st.get("frozen_k")  # frozen prefix: the loop stops above block fk and the tokeniser's backward is not launched
         k0 = 0 if fk is None else fk
@@ -1260,7 +1359,8 @@ class DiChaViT(nn.Module):
         b = types.SimpleNamespace(B=B, N=N, M=M, g=g, nt_kw=nt_kw, ps=bool(st.get("ps")), sc=sc,
                                   du=torch.empty(Ms, D, dtype=bf, device=dev), dO=torch.empty(Ms, D, dtype=bf, device=dev),
                                   delta=torch.empty(2, B, H, N if Ms else 0, dtype=f32, device=dev),  # attention backward workspace: -delta, lse*log2e
-                                  probe=st.get("probe"))  # get_attention_relevance: called with (L, b) once a block's b.dO is written
+                                  probe=st.get("probe"),  # get_attention_relevance: called with (L, b) once a block's b.dO is written
+                                  taps=tp, dtaps=dtaps)  # feature taps still to be added: {block: gradient}
         for li in range(len(fe.blocks) - 1, k0 - 1, -1):
             blk = fe.blocks[li]
             below = st["layers"][li - 1].get("drop") if li > 0 else None
@@ -1270,6 +1370,11 @@ class DiChaViT(nn.Module):
                 # side stream — made to wait for this layer's last LayerNorm-backward on the main stream — is behind every writer
                 # of the slice; the main stream itself never waits for the weight gradients here
                 with sc.on_side():
+                    if norm_after == li:
+                        # the lowest tap's term is in (this block's backward added it on the main stream): the final norm's bucket.  Also from
+                        # the side stream: grad_ready launches what is pending — the slices of the blocks above, written by side-stream GEMMs —
+                        # when the new range is not adjacent to it, and the norm's never is
+                        dp.grad_ready(ga, *self._range_of([fe.norm.weight, fe.norm.bias]))
                     dp.grad_ready(ga, *self._range_of([blk.norm1.weight, blk.mlp.fc2.bias]))
         sc.join()
         if b.probe is not None:  # an inspection call: the walk ends above block k0, no gradient leaves
@@ -1325,6 +1430,11 @@ class DiChaViT(nn.Module):
         hip.gemm_nt(sc.dqkv, self._bf(blk.attn.qkv.weight, True), hip.EPI_PLAIN_BF16, b.du, **nt_kw)
         sc.wgrad(sc.dqkv, L["u1"], g(blk.attn.qkv.weight), g(blk.attn.qkv.bias))
         sc.launch_group()
+        if li - 1 in b.dtaps:
+            # the tap on the stream this block read (block li - 1's output, L["x_in"]): its gradient joins dx after norm2's backward — the copy
+            # that fed this block's attention branch must not carry it — and before norm1's, whose launch writes the bf16 copy for the block
+            # below from the sum (DropPath factor included): no cast pass of its own
+            self._tap_backward(b.taps, li - 1, b.dtaps.pop(li - 1), dx, g, B, N)
         # At the first trainable block above a frozen prefix (li == k0 > 0) nobody reads what this launch writes for the block below (dx,
         # and dxb with that block's DropPath factors): the loop ends here.  The launch stays as it is, for norm1's own weight and bias
         # gradients come out of the same kernel, which reads the full-size dx as the residual gradient (the CLS-only tail's zero-filled
@@ -1416,8 +1526,46 @@ class DiChaViT(nn.Module):
         with torch.autocast(device_type="cuda", enabled=False):
             return self._forward_impl(x, chunk_name, training_chunks, init_first_layer, new_channel_init, **kwargs)
 
+    def forward_with_features(self, x: torch.Tensor, chunk_name: str, training_chunks: Optional[str] = None, *, layers=4, pool="channel",
+                              init_first_layer=None, new_channel_init=None, **kwargs):
+        """forward() with differentiable feature taps: returns (out, feats).  `out` is what model(x, chunk_name, training_chunks, ...) returns
+        in the same mode, from the same training or eval forward (operand copies, stochastic rounding, HCS draw, DropPath, DataParallel's
+        begin_forward(), saved state).  `feats` lists, in block order, the residual stream after each block of `layers` (parsed as
+        get_intermediate_layers parses n: an int asks for the last blocks, a sequence names them) with the encoder's final norm applied, fp32 and
+        CONNECTED to the graph: a loss on them reaches the parameters — and x, when it requires a gradient — through the hand-written backward.
+        pool="channel": [B, 1 + C, D], CLS and one mean patch token per channel (dcv_ln_pool_channels; backward: dcv_ln_pool_channels_bwd);
+        pool="cls": [B, D]; pool=None: [B, N, D].  C and N are this forward's (the sampled channels under HCS).  pool="channel" under active
+        token drop raises ValueError, as in get_intermediate_layers.
+        The last block runs on all rows instead of as the CLS-only tail when it is tapped with a pool other than "cls"; nothing else in the
+        forward changes, and with the tail in the same state `out` has the bits of the plain forward's.  Under no_grad in eval mode every entry
+        has the bits of get_intermediate_layers' on the same input.
+        The gradient of a tap joins the fp32 stream gradient after its block; norm.weight and norm.bias receive theirs in the slots
+        of the final norm's own backward.  A tap without a gradient launches nothing in the backward; a loss on the taps alone works.  With
+        freeze_prefix(k) a tap at block l >= k - 1 works (at l = k - 1 its gradient reaches only `norm`); one below raises ValueError — no
+        trainable block could receive it, and get_intermediate_layers returns that feature.
+        Not supported: GraphedTrainStep, create_graph=True, several pools in one call."""
+        depth = len(self.feature_extractor.blocks)
+        blocks = _parse_layers(layers, depth)
+        if pool not in (None, "channel", "cls"):
+            raise ValueError(f"pool={pool!r}: expected 'channel', 'cls' or None")
+        _check_taps_above_prefix(blocks, self._host_frozen_prefix(x))
+        with torch.autocast(device_type="cuda", enabled=False):
+            return self._forward_impl(x, chunk_name, training_chunks, init_first_layer, new_channel_init, taps=(blocks, pool), **kwargs)
+
+    def _host_frozen_prefix(self, x) -> Optional[int]:
+        """_frozen_prefix as _EncoderFn will find it for a forward of x, from requires_grad flags alone (no device work): upstream of the blocks are
+        x and what the node's E, pos_tab, cls_token and patch-projection inputs come from."""
+        if not torch.is_grad_enabled():
+            return None
+        fe = self.feature_extractor
+        pe = fe.patch_embed
+        up = [fe.cls_token, fe.pos_embed, pe.proj.weight, pe.proj.bias] + ([pe.channel_embed.weight] if hasattr(pe, "channel_embed") else [])
+        upstream = (torch.is_tensor(x) and x.requires_grad) or any(p.requires_grad for p in up)
+        return _frozen_prefix(upstream, [any(p.requires_grad for p in blk.parameters()) for blk in fe.blocks],
+                              any(p.requires_grad for p in fe.norm.parameters()), self._dp)
+
     def _forward_impl(self, x: torch.Tensor, chunk_name: str, training_chunks: Optional[str] = None, init_first_layer=None,
-                      new_channel_init=None, **kwargs):
+                      new_channel_init=None, taps=None, **kwargs):
         self._check_input(x)
         if self._dp is not None and self.training:
             self._dp.begin_forward()
@@ -1426,7 +1574,14 @@ class DiChaViT(nn.Module):
         x, C, n, want_ortho, cur_channels, channel_embed = tk.x, tk.C, tk.n, tk.want_ortho, tk.cur_channels, tk.channel_embed
         lam_o, lam_p = tk.lam_o, tk.lam_p
         pe = self.feature_extractor.patch_embed
-        feat, stats = _EncoderFn.apply(self, tk.ch_idx_dev, C, want_ortho, tk.keep, tk.tok, x, tk.E_tok, tk.pos_tab, *self._enc_params)
+        feats = None
+        if taps is not None:
+            if taps[1] == "channel" and tk.keep is not None:
+                raise ValueError("pool='channel' needs every channel's n_p patch tokens: with dropout_tokens_hcs active in train mode the channel "
+                                 "segments are ragged (pool=None returns the kept tokens)")
+            feat, stats, *feats = _EncoderTapsFn.apply(taps, self, tk.ch_idx_dev, C, want_ortho, tk.keep, tk.tok, x, tk.E_tok, tk.pos_tab, *self._enc_params)
+        else:
+            feat, stats = _EncoderFn.apply(self, tk.ch_idx_dev, C, want_ortho, tk.keep, tk.tok, x, tk.E_tok, tk.pos_tab, *self._enc_params)
         # --- regularisers (tiny tensors; models/loss_fn.py) ---
         extra = 0
         if want_ortho:
@@ -1442,8 +1597,8 @@ class DiChaViT(nn.Module):
         if self.training:
             if isinstance(extra, int) and extra == 0:
                 extra = out.new_zeros(())  # :857-858 (a device-side fill: torch.tensor(0.0, device=...) is a synchronising host-to-device copy)
-            return out, extra
-        return out
+            out = (out, extra)
+        return out if feats is None else (out, feats)
 
     @staticmethod
     def _check_input(x: torch.Tensor) -> None:

@@ -34,6 +34,8 @@ _SIGS = {
     "dcv_ln_fwd": ([_vp, _l, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _f, _vp], _i),
     "dcv_ln_pool_channels_ws_floats": ([_i, _i, _i, _i], _l),
     "dcv_ln_pool_channels": ([_vp, _vp, _vp, _f, _vp, _i, _i, _i, _i, _vp, _l, _vp], _i),
+    "dcv_ln_pool_channels_bwd_ws_floats": ([_i, _i, _i, _i], _l),
+    "dcv_ln_pool_channels_bwd": ([_vp, _vp, _f, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _l, _vp], _i),
     "dcv_ln_bwd": ([_vp, _i, _vp, _l, _vp, _vp, _vp, _vp, _vp, _l, _vp, _vp, _vp, _i, _i, _vp], _i),
     "dcv_ln_bwd_det_ws_floats": ([_i, _i], _l),
     "dcv_ln_bwd_det": ([_vp, _i, _vp, _l, _vp, _vp, _vp, _vp, _vp, _l, _vp, _vp, _vp, _i, _i, _vp, _l, _vp], _i),
@@ -369,6 +371,29 @@ def ln_pool_channels(x, gamma, beta, out, B, C, n_p, D, eps, ws=None):
         rc = lib.dcv_ln_pool_channels(_p(x), _p(gamma), _p(beta), float(eps), _p(out), B, C, n_p, D, _p(ws), ws.numel() if ws is not None else 0,
                                       _stream())
     _check(rc, "dcv_ln_pool_channels")
+
+
+def ln_pool_channels_bwd(x, gamma, dout, dx, dgamma, dbeta, B, C, n_p, D, eps, ws=None):
+    """Adjoint of ln_pool_channels: dx [B, 1 + C * n_p, D] += the gradient of the pooled LayerNorm for dout [B, 1 + C, D]; dgamma / dbeta [D]
+    (each may be None) accumulated (include/dcv.h: dcv_ln_pool_channels_bwd).  Always the deterministic form: the kernel has no
+    other.  ws: the caller's workspace (tests); by default the stream's shared one."""
+    _req(x, torch.float32, "x"); _req(gamma, torch.float32, "gamma"); _req(dout, torch.float32, "dout"); _req(dx, torch.float32, "dx")
+    if x.numel() < B * (1 + C * n_p) * D or dx.numel() < B * (1 + C * n_p) * D or dout.numel() < B * (1 + C) * D or gamma.numel() < D:
+        raise ValueError("ln_pool_channels_bwd: x and dx hold B*(1+C*n_p)*D floats, dout B*(1+C)*D, gamma D")
+    for t, name in ((dgamma, "dgamma"), (dbeta, "dbeta")):
+        if t is not None:
+            _req(t, torch.float32, name)
+            if t.numel() < D:
+                raise ValueError(f"ln_pool_channels_bwd: {name} holds D floats")
+    lib = load()
+    with _timer(lambda: (f"ln_pool_bwd_kernel<{2 if D <= 512 else 4}>", f"B{B} C{C} n{n_p} D{D}", 0.0, None, 4.0 * D * B * (3 * (1 + C * n_p) + 1 + C))):
+        if ws is None:
+            ws = _workspace(_ws_size(lib.dcv_ln_pool_channels_bwd_ws_floats(B, C, n_p, D)), dx) if dgamma is not None else None
+        else:
+            _req(ws, torch.float32, "ws")
+        rc = lib.dcv_ln_pool_channels_bwd(_p(x), _p(gamma), float(eps), _p(dout), _p(dx), _p(dgamma), _p(dbeta), B, C, n_p, D, _p(ws),
+                                          ws.numel() if ws is not None else 0, _stream())
+    _check(rc, "dcv_ln_pool_channels_bwd")
 
 
 def ln_bwd(du, x, mean, rstd, gamma, dx_in, dx_out, dx_bf16, dgamma, dbeta, M, D, x_row_stride=None, dx_row_stride=None,

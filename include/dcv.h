@@ -137,6 +137,21 @@ int dcv_ln_bwd(const void* du, int du_is_f32, const float* x, long x_row_stride,
 long dcv_ln_pool_channels_ws_floats(int B, int C, int n_p, int D);
 int dcv_ln_pool_channels(const float* x, const float* gamma, const float* beta, float eps, float* out, int B, int C, int n_p, int D,
                          float* ws, long ws_floats, void* stream);
+/* Adjoint of dcv_ln_pool_channels (DiChaViT.forward_with_features, pool="channel"): with g = dout[b, 1 + c], h = gamma * g / n_p and
+ * x^_i = (x_i - mu_i) rstd_i for row i of segment (b, c),
+ *   dx_i += rstd_i (h - mean_D(h) - x^_i mean_D(h x^_i))    (the CLS row: the same with n_p = 1 and g = dout[b, 0]);
+ *   dgamma += sum_b dout[b, 0] x^_cls + sum_{b,c} dout[b, 1 + c] (1 / n_p) sum_i x^_i;    dbeta += sum_{b,j} dout[b, j].
+ * x f32 [B, N, D], N = 1 + C * n_p; dout f32 [B, 1 + C, D]; dx f32 [B, N, D] is ACCUMULATED in place; dgamma / dbeta f32 [D] are accumulated and
+ * may each be NULL (dx has the same bits).  One pass: x is read once, dx read and written once, the broadcast of g never exists in memory;
+ * mu and rstd are recomputed from the row exactly as dcv_ln_fwd and dcv_ln_pool_channels form them.  No atomics: every row of dx belongs to one
+ * wave, the dgamma partials of the workgroups go through ws and are added in workgroup order, dbeta adds the rows of dout in row order — every
+ * order is a function of (B, C, n_p, D) alone, two calls are bit-identical.  The split of a segment's rows over workgroups is that of
+ * dcv_ln_pool_channels; ws: at least dcv_ln_pool_channels_bwd_ws_floats(B, C, n_p, D) = (B C S + ceil(B / 4)) D floats (not read when dgamma is
+ * NULL), contents irrelevant.  D % 4 == 0, D <= 1024 and ws_floats large enough, else DCV_ERR_SHAPE; every pointer 16-byte aligned, else
+ * DCV_ERR_ALIGN. */
+long dcv_ln_pool_channels_bwd_ws_floats(int B, int C, int n_p, int D);
+int dcv_ln_pool_channels_bwd(const float* x, const float* gamma, float eps, const float* dout, float* dx, float* dgamma, float* dbeta,
+                             int B, int C, int n_p, int D, float* ws, long ws_floats, void* stream);
 
 /* DETERMINISTIC forms of the other entries that combine partial sums of several workgroups (LayerNorm's dgamma / dbeta, the tokeniser's
  * d(channel_embed) / d(pos), the diversity loss' per-channel sums, the gradient norm): partials go through `ws` (at least *_det_ws_floats
