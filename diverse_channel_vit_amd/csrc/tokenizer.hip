@@ -193,7 +193,7 @@ __global__ __launch_bounds__(256) void ortho_zero_kernel(float* __restrict__ S, 
 
 // per image: tot = sum_c s_c ; stats = (pos_sum, neg_sum)
 __global__ __launch_bounds__(256) void ortho_fwd_final(const float* __restrict__ S, const float* __restrict__ selfsq,
-                                                       float* __restrict__ tot, float* __restrict__ stats, int C, int D) {
+                                                       float* __restrict__ tot, float* __restrict__ stats, int C, int n, int D) {
     __shared__ float red[3][4];
     const int b = blockIdx.x;
     float ssq = 0.f, tsq = 0.f;
@@ -223,7 +223,7 @@ __global__ __launch_bounds__(256) void ortho_fwd_final(const float* __restrict__
         float a = red[0][0] + red[0][1] + red[0][2] + red[0][3];
         float t2 = red[1][0] + red[1][1] + red[1][2] + red[1][3];
         float sf = red[2][0] + red[2][1] + red[2][2] + red[2][3];
-        stats[2 * b] = a - sf;                 // pos_sum
+        stats[2 * b] = (n == 1) ? 0.f : (a - sf);      // pos_sum (exactly 0 when no same-channel pair exists)
         stats[2 * b + 1] = (C == 1) ? 0.f : (t2 - a);  // neg_sum (exactly 0 when no different-channel pair exists)
     }
 }
@@ -374,7 +374,7 @@ static int ortho_fwd_launch(const float* Y, float* S, float* selfsq, float* tot,
     }
     hipLaunchKernelGGL(ortho_fwd_partial, grid, dim3(256), 0, s, Y, S, selfsq, inv_norm, C, n, D, ws);
     if (ws && !det_reduce(ws, (int)grid.x, nS + nQ, S, nS, D, D, selfsq, nQ, s)) return DCV_ERR_LAUNCH;
-    hipLaunchKernelGGL(ortho_fwd_final, dim3(B), dim3(256), 0, s, S, selfsq, tot, stats, C, D);
+    hipLaunchKernelGGL(ortho_fwd_final, dim3(B), dim3(256), 0, s, S, selfsq, tot, stats, C, n, D);
     DCV_LAUNCH_CHECK();
     return DCV_OK;
 }

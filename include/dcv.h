@@ -310,7 +310,8 @@ int dcv_crop_resize_flip(const void* x, int x_is_u8, const float* warped, const 
                          int B, int C, int H, int W, int S, void* stream);
 
 /* ortho_proj_loss_fn_v2 statistics (loss_fn.py:24-48): stats[b] = (pos_sum, neg_sum) of image b.
- * S [B,C,D], selfsq [B,C], tot [B,D], inv_norm [B,C*n] are outputs kept for the backward. */
+ * S [B,C,D], selfsq [B,C], tot [B,D], inv_norm [B,C*n] are outputs kept for the backward.
+ * pos_sum is exactly 0 when n == 1 and neg_sum exactly 0 when C == 1: no such pair exists, and the caller divides by a count of 1e-6. */
 int dcv_ortho_fwd(const float* Y, float* S, float* selfsq, float* tot, float* inv_norm, float* stats, int B, int C, int n, int D,
                   void* stream);
 /* dY [B,C*n,D] f32 = d loss / dY given coef[b] = (dL/dpos_sum_b, dL/dneg_sum_b). */
