@@ -38,7 +38,9 @@ struct AttnArgs {
 // blockIdx -> (batch-head, 128-query tile) of the forward and dQ kernels.  An XCD gets all tiles of a batch-head (its K / V stay in that XCD's L2).
 // DCV_ATTN_LIGHT_LAST (variant builds): when the last query tile is ragged (N = 1569: 33 of 128 rows, two of its four waves idle), those light workgroups
 // are numbered AFTER all full ones, so that the full tiles fill whole rounds of resident workgroups and the light ones share the tail round.  Measured: no
-// change (forward 300 -> 306 us, dQ 385 -> 380, inside the run-to-run spread; profiles/r05_x8_* (c)); off in the product.
+// change (forward 300 -> 306 us, dQ 385 -> 380, inside the run-to-run spread; profiles/r05_x8_* (c)); off in the product.  The forward and dQ grids are
+// exactly BH * nqt, so the else arm below is unreachable while the knob is off; kernels built without the arm differed by 0.2-0.7 us in an interleaved
+// A/B, which is what identical code differs by in the same table (profiles/retired_variants_ab.txt).
 #ifndef DCV_ATTN_LIGHT_LAST
 #define DCV_ATTN_LIGHT_LAST 0
 #endif

@@ -1021,8 +1021,11 @@ __global__ __launch_bounds__(512) void gemm_nt384_kernel(GemmNtArgs a) {
 #ifndef DCV_NT_WS
 #define DCV_NT_WS 1
 #endif
+constexpr int WS_BM = 32, WS_BN = 384, WS_WAVES = 12;
+template <int EPI>
+__global__ void gemm_nt_ws_kernel(GemmNtArgs a);  // declared in every build, so that the host code needs no #if; defined where DCV_NT_WS is on
 #if DCV_NT_WS
-constexpr int WS_BM = 32, WS_BN = 384, WS_K = 384, WS_WAVES = 12;
+constexpr int WS_K = 384;
 constexpr int WS_A_BYTES = WS_BM * WS_K * 2;     // 24 KB: 6 k-chunks of [32 rows][64] (128-byte rows, swz64n), 24 DMA pieces = 2 per wave
 constexpr int WS_AUX_BYTES = WS_BM * WS_BN * 2;  // 24 KB: [wave][row block][lane] x 16 B, 2 pieces per wave
 template <int EPI>
@@ -1184,41 +1187,20 @@ __global__ __launch_bounds__(64 * WS_WAVES) void gemm_nt_ws_kernel(GemmNtArgs a)
 
 }  // namespace
 
-#define DCV_NT_CASES(KERNEL, G) DCV_NT_CASES_T(KERNEL, G, 512)
-#define DCV_NT_CASES_T(KERNEL, G, THREADS)                                                             \
-    switch (epilogue) {                                                                                \
-        case DCV_EPI_BIAS_BF16:                                                                        \
-            if (!bias) return DCV_ERR_NULL;                                                            \
-            hipLaunchKernelGGL(KERNEL<DCV_EPI_BIAS_BF16>, dim3(G), dim3(THREADS), 0, s, a);                \
-            break;                                                                                     \
-        case DCV_EPI_BIAS_GELU_BF16:                                                                   \
-            if (!bias || !out2) return DCV_ERR_NULL;                                                   \
-            hipLaunchKernelGGL(KERNEL<DCV_EPI_BIAS_GELU_BF16>, dim3(G), dim3(THREADS), 0, s, a);           \
-            break;                                                                                     \
-        case DCV_EPI_BIAS_RESID_F32:                                                                   \
-            if (!bias) return DCV_ERR_NULL;                                                            \
-            hipLaunchKernelGGL(KERNEL<DCV_EPI_BIAS_RESID_F32>, dim3(G), dim3(THREADS), 0, s, a);           \
-            break;                                                                                     \
-        case DCV_EPI_PLAIN_BF16:                                                                       \
-            hipLaunchKernelGGL(KERNEL<DCV_EPI_PLAIN_BF16>, dim3(G), dim3(THREADS), 0, s, a);               \
-            break;                                                                                     \
-        case DCV_EPI_GELU_BWD_BF16:                                                                    \
-            if (!aux) return DCV_ERR_NULL;                                                             \
-            hipLaunchKernelGGL(KERNEL<DCV_EPI_GELU_BWD_BF16>, dim3(G), dim3(THREADS), 0, s, a);            \
-            break;
-
 // DCV_TILE_AUTO_WS: the weight-stationary kernel from this many rows on (below, its one-off weight load and the few panels per CU
 // do not pay; the 64-row CLS tail stays on the tiled kernels)
 #ifndef DCV_WS_M_MIN
 #define DCV_WS_M_MIN 8192
 #endif
+// the epilogues gemm_nt_ws_kernel is written for
+constexpr bool nt_ws_takes(int epilogue) {
+    return epilogue == DCV_EPI_BIAS_BF16 || epilogue == DCV_EPI_BIAS_GELU_BF16 || epilogue == DCV_EPI_PLAIN_BF16 || epilogue == DCV_EPI_GELU_BWD_BF16;
+}
 // which kernel dcv_gemm_nt_ex launches for this problem (DCV_TILE_NARROW / _WIDE / _PAIR / _WS), or a negative error for an illegal forced tile
 extern "C" int dcv_gemm_nt_pick(int M, int N, int K, int epilogue, int tile) {
     if (tile < DCV_TILE_AUTO || tile > DCV_TILE_AUTO_WS) return DCV_ERR_SHAPE;
     const bool legal384 = (N % N3_BN) == 0 && epilogue != DCV_EPI_PATCH;
-    const bool legal_ws = DCV_NT_WS && K == 384 && (N % 384) == 0 &&
-                          (epilogue == DCV_EPI_BIAS_BF16 || epilogue == DCV_EPI_BIAS_GELU_BF16 || epilogue == DCV_EPI_PLAIN_BF16 ||
-                           epilogue == DCV_EPI_GELU_BWD_BF16);
+    const bool legal_ws = DCV_NT_WS && K == 384 && (N % 384) == 0 && nt_ws_takes(epilogue);
     if (tile == DCV_TILE_WS) return legal_ws ? DCV_TILE_WS : DCV_ERR_UNSUPPORTED;
     if (tile == DCV_TILE_AUTO_WS) {
         // the weight-stationary kernel where it measured faster (tools/gemm_bench.py), else AUTO's choice
@@ -1283,6 +1265,58 @@ extern "C" int dcv_gemm_nt384_plan(int M, int N, int grid, int* n256, int* n192)
     return DCV_OK;
 }
 
+// what an epilogue needs beyond A, W and out: its pointers, and for PATCH the shape of its embedding tables
+static int nt_epilogue_check(int epilogue, const GemmNtArgs& a) {
+    switch (epilogue) {
+        case DCV_EPI_BIAS_BF16:
+        case DCV_EPI_BIAS_RESID_F32: return a.bias ? DCV_OK : DCV_ERR_NULL;
+        case DCV_EPI_BIAS_GELU_BF16: return a.bias && a.out2 ? DCV_OK : DCV_ERR_NULL;
+        case DCV_EPI_PLAIN_BF16: return DCV_OK;
+        case DCV_EPI_GELU_BWD_BF16: return a.aux ? DCV_OK : DCV_ERR_NULL;
+        case DCV_EPI_PATCH:
+            return a.bias && a.aux && a.aux2 && a.T > 0 && a.n > 0 && (a.M % a.T) == 0 && (a.T % a.n) == 0 ? DCV_OK : DCV_ERR_SHAPE;
+        default: return DCV_ERR_UNSUPPORTED;
+    }
+}
+
+// launches the picked kernel (dcv_gemm_nt_pick) on that kernel's grid of at most `cap` workgroups; a combination that has no kernel is refused
+template <int EPI>
+static int nt_launch(int pick, GemmNtArgs& a, int cap, hipStream_t s) {
+    if (pick == DCV_TILE_WS) {
+        if constexpr (DCV_NT_WS && nt_ws_takes(EPI)) {
+            // whole groups of N / 384 workgroups (one per weight slice), at most one group per 32-row panel; a CU count that the slice count does
+            // not divide leaves the remainder idle (qkv: 85 groups of 3 on 256 CUs)
+            const int slices = a.N / WS_BN, panels = (a.M + WS_BM - 1) / WS_BM;
+            const int groups = std::min(cap / slices, panels);
+            hipLaunchKernelGGL(gemm_nt_ws_kernel<EPI>, dim3(groups * slices), dim3(64 * WS_WAVES), 0, s, a);
+        } else
+            return DCV_ERR_UNSUPPORTED;
+    } else if (pick == DCV_TILE_WIDE) {
+        if constexpr (EPI != DCV_EPI_PATCH) {
+            int g3 = ((a.M + N3_BM - 1) / N3_BM) * (a.N / N3_BN);
+            if (g3 > cap) g3 = cap;
+            int n192;
+            dcv_gemm_nt384_plan(a.M, a.N, g3, &a.n256, &n192);  // the grid is min(tiles, cap) under either plan: a plan with 192-row tiles has more than one round
+            a.tiles_m = a.n256 + n192;
+            hipLaunchKernelGGL(gemm_nt384_kernel<EPI>, dim3(g3), dim3(512), 0, s, a);
+        } else
+            return DCV_ERR_UNSUPPORTED;  // the tokeniser epilogue exists on the 256 x 128 kernel only
+    } else if (pick == DCV_TILE_PAIR) {
+        if constexpr (EPI != DCV_EPI_PATCH) {
+            int gp = ((a.M + NP_BM - 1) / NP_BM) * ((a.N + NP_BN - 1) / NP_BN);
+            if (gp > 2 * cap) gp = 2 * cap;  // two workgroups per CU
+            hipLaunchKernelGGL(gemm_nt_pair_kernel<EPI>, dim3(gp), dim3(256), 0, s, a);
+        } else
+            return DCV_ERR_UNSUPPORTED;
+    } else {
+        int grid = ((a.M + NT_BM - 1) / NT_BM) * ((a.N + NT_BN - 1) / NT_BN);
+        if (grid > cap) grid = cap;
+        hipLaunchKernelGGL(gemm_nt_kernel<EPI>, dim3(grid), dim3(512), 0, s, a);
+    }
+    DCV_LAUNCH_CHECK();
+    return DCV_OK;
+}
+
 extern "C" int dcv_gemm_nt_ex(const void* A, int lda, const void* W, int ldw, int M, int N, int K, int epilogue,
                               const float* bias, void* out, int ldo, void* out2, int ldo2, const void* aux, int ldaux,
                               const float* aux2, int T, int n, int grid_cap, int tile, void* stream) {
@@ -1311,79 +1345,23 @@ extern "C" int dcv_gemm_nt_ex(const void* A, int lda, const void* W, int ldw, in
     // rows high; the choice was not re-tuned), and the GELU-backward epilogue (N = 1536, HBM-heavy: 616 MB in + out) 212 -> 220.  tile = DCV_TILE_WIDE forces the 256 x 384 kernel wherever it is legal, DCV_TILE_NARROW never uses it.
     int pick = dcv_gemm_nt_pick(M, N, K, epilogue, tile);
     if (pick < 0) return pick;
-#if DCV_NT_WS
     if (pick == DCV_TILE_WS && cap < N / WS_BN) {  // fewer workgroups than weight slices: only the tiled kernels can run under this cap
         if (tile == DCV_TILE_WS) return DCV_ERR_UNSUPPORTED;
         pick = dcv_gemm_nt_pick(M, N, K, epilogue, DCV_TILE_AUTO);
     }
-    if (pick == DCV_TILE_WS) {
-        // whole groups of N / 384 workgroups (one per weight slice), at most one group per 32-row panel; a CU count that the slice count does
-        // not divide leaves the remainder idle (qkv: 85 groups of 3 on 256 CUs)
-        if ((ldo2 % 8) || (ldaux % 8) || ((uintptr_t)out2 & 15) || ((uintptr_t)aux & 15) || ((uintptr_t)bias & 15)) return DCV_ERR_ALIGN;
-        const int slices = N / WS_BN, panels = (M + WS_BM - 1) / WS_BM;
-        const int groups = std::min(cap / slices, panels);
-        const int gw = groups * slices;
-        switch (epilogue) {
-            case DCV_EPI_BIAS_BF16:
-                if (!bias) return DCV_ERR_NULL;
-                hipLaunchKernelGGL(gemm_nt_ws_kernel<DCV_EPI_BIAS_BF16>, dim3(gw), dim3(64 * WS_WAVES), 0, s, a);
-                break;
-            case DCV_EPI_BIAS_GELU_BF16:
-                if (!bias || !out2) return DCV_ERR_NULL;
-                hipLaunchKernelGGL(gemm_nt_ws_kernel<DCV_EPI_BIAS_GELU_BF16>, dim3(gw), dim3(64 * WS_WAVES), 0, s, a);
-                break;
-            case DCV_EPI_PLAIN_BF16:
-                hipLaunchKernelGGL(gemm_nt_ws_kernel<DCV_EPI_PLAIN_BF16>, dim3(gw), dim3(64 * WS_WAVES), 0, s, a);
-                break;
-            case DCV_EPI_GELU_BWD_BF16:
-                if (!aux) return DCV_ERR_NULL;
-                hipLaunchKernelGGL(gemm_nt_ws_kernel<DCV_EPI_GELU_BWD_BF16>, dim3(gw), dim3(64 * WS_WAVES), 0, s, a);
-                break;
-            default:
-                return DCV_ERR_UNSUPPORTED;
-        }
-        DCV_LAUNCH_CHECK();
-        return DCV_OK;
+    // its 16-byte pieces of the optional buffers (checked before the epilogue's own needs)
+    if (pick == DCV_TILE_WS && ((ldo2 % 8) || (ldaux % 8) || ((uintptr_t)out2 & 15) || ((uintptr_t)aux & 15) || ((uintptr_t)bias & 15))) return DCV_ERR_ALIGN;
+    if (const int err = nt_epilogue_check(epilogue, a)) return err;
+    switch (epilogue) {
+        case DCV_EPI_BIAS_BF16: return nt_launch<DCV_EPI_BIAS_BF16>(pick, a, cap, s);
+        case DCV_EPI_BIAS_GELU_BF16: return nt_launch<DCV_EPI_BIAS_GELU_BF16>(pick, a, cap, s);
+        case DCV_EPI_BIAS_RESID_F32: return nt_launch<DCV_EPI_BIAS_RESID_F32>(pick, a, cap, s);
+        case DCV_EPI_PLAIN_BF16: return nt_launch<DCV_EPI_PLAIN_BF16>(pick, a, cap, s);
+        case DCV_EPI_GELU_BWD_BF16: return nt_launch<DCV_EPI_GELU_BWD_BF16>(pick, a, cap, s);
+        case DCV_EPI_PATCH: return nt_launch<DCV_EPI_PATCH>(pick, a, cap, s);
     }
-#endif
-    if (pick == DCV_TILE_WIDE) {
-        int g3 = ((M + N3_BM - 1) / N3_BM) * (N / N3_BN);
-        if (g3 > cap) g3 = cap;
-        int n192;
-        dcv_gemm_nt384_plan(M, N, g3, &a.n256, &n192);  // the grid is min(tiles, cap) under either plan: a plan with 192-row tiles has more than one round
-        a.tiles_m = a.n256 + n192;
-        DCV_NT_CASES(gemm_nt384_kernel, g3)
-            default:
-                return DCV_ERR_UNSUPPORTED;
-        }
-        DCV_LAUNCH_CHECK();
-        return DCV_OK;
-    }
-    if (pick == DCV_TILE_PAIR) {
-        int gp = ((M + NP_BM - 1) / NP_BM) * ((N + NP_BN - 1) / NP_BN);
-        if (gp > 2 * cap) gp = 2 * cap;  // two workgroups per CU
-        DCV_NT_CASES_T(gemm_nt_pair_kernel, gp, 256)
-            default:
-                return DCV_ERR_UNSUPPORTED;
-        }
-        DCV_LAUNCH_CHECK();
-        return DCV_OK;
-    }
-    int grid = ((M + NT_BM - 1) / NT_BM) * ((N + NT_BN - 1) / NT_BN);
-    if (grid > cap) grid = cap;
-    DCV_NT_CASES(gemm_nt_kernel, grid)
-        case DCV_EPI_PATCH:
-            if (!bias || !aux || !aux2 || T <= 0 || n <= 0 || (M % T) != 0 || (T % n) != 0) return DCV_ERR_SHAPE;
-            hipLaunchKernelGGL(gemm_nt_kernel<DCV_EPI_PATCH>, dim3(grid), dim3(512), 0, s, a);
-            break;
-        default:
-            return DCV_ERR_UNSUPPORTED;
-    }
-    DCV_LAUNCH_CHECK();
-    return DCV_OK;
+    return DCV_ERR_UNSUPPORTED;  // (nt_epilogue_check let no other value through)
 }
-#undef DCV_NT_CASES
-#undef DCV_NT_CASES_T
 
 extern "C" int dcv_gemm_nt_resid_ln(const void* A, int lda, const void* W, int ldw, int M, int N, int K, const float* bias, const float* resid,
                                     int ldr, const float* branch_scale, int T, float* x_out, int ldo, const float* gamma, const float* beta,

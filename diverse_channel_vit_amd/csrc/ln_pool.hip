@@ -23,7 +23,7 @@
 // for dcv_ln_fwd (fp32 output) + torch.mean and 29.9 us for a copy that moves the same bytes (1.85 x that floor, 2.8 TB/s); C 3
 // 30.8 / 41.0 / 12.0 us.  The split plan pays even where B C already covers the CUs: asking for 512 workgroups (DCV_LP_TARGET_WGS=512 —
 // whole segments at C 8, no workspace, no second launch) takes 69.2 us at C 8 and 32.3 us at C 3; two workgroups of four waves per CU
-// leave too few loads in flight.  A wave keeps ONE row's loads in flight: with two (DCV_LP_TWO_ROWS=1, the same summation order) the
+// leave too few loads in flight.  A wave keeps ONE row's loads in flight: with two (a retired variant, the same summation order) the
 // split plan measured 56.2 vs 55.2 us at C 8 and 31.9 vs 30.8 us at C 3, and the 512-workgroup plan 82.6 vs 69.2 us and 35.4 vs 32.3 us
 // — never faster, as ln_fwd_kernel found for its own loop.  LP_MIN_ROWS = 8 has not been varied.  What holds the kernel at 1.85 x the
 // copy floor has not been profiled.
@@ -32,10 +32,6 @@
 #include "ln_pool_plan.hpp"  // lp_plan, lp_shape_ok and their constants: shared with ln_pool_bwd.hip
 
 namespace {
-
-#ifndef DCV_LP_TWO_ROWS
-#define DCV_LP_TWO_ROWS 0  // 1 (variant builds): two rows' loads in flight per wave; measured no faster (header), as in ln_fwd_kernel
-#endif
 
 // Workgroups [0, B C S): one (segment, split) each.  Workgroups from B C S on: four CLS rows each (one per wave).
 template <int MAXV>
@@ -115,26 +111,11 @@ __global__ __launch_bounds__(256) void ln_pool_kernel(const float* __restrict__ 
         }
     };
     int r = r0 + wave;
-#if DCV_LP_TWO_ROWS
-    for (; r + 4 < r1; r += 8) {  // two rows' loads in flight per wave; added in row order
-        f32x4 va[MAXV], vb[MAXV];
-        load_row(xs + (size_t)r * D, va);
-        load_row(xs + (size_t)(r + 4) * D, vb);
-        add_row(va);
-        add_row(vb);
-    }
-    if (r < r1) {
-        f32x4 va[MAXV];
-        load_row(xs + (size_t)r * D, va);
-        add_row(va);
-    }
-#else
     for (; r < r1; r += 4) {
         f32x4 va[MAXV];
         load_row(xs + (size_t)r * D, va);
         add_row(va);
     }
-#endif
     if (wave > 0) {
 #pragma unroll
         for (int i = 0; i < MAXV; ++i) red[wave - 1][i][lane] = acc[i];

@@ -12,17 +12,7 @@ namespace {
 #ifndef DCV_LN_NT
 #define DCV_LN_NT 1
 #endif
-#ifndef DCV_LN_FWD_ROWS
-#define DCV_LN_FWD_ROWS 1
-#endif
-#ifndef DCV_LN_NT_ST
-#define DCV_LN_NT_ST 0  // measured: non-temporal stores +1.5..2 us on both kernels (and the next GEMM re-reads these rows)
-#endif
-#if DCV_LN_NT_ST
-#define LN_STORE(p, v) __builtin_nontemporal_store(v, p)
-#else
-#define LN_STORE(p, v) (*(p) = (v))
-#endif
+// the stores are plain.  Measured: non-temporal stores +1.5..2 us on both kernels (and the next GEMM re-reads these rows)
 #if DCV_LN_NT
 #define LN_LOAD(p) __builtin_nontemporal_load(p)
 #else
@@ -76,26 +66,15 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x
                 float o0 = (v[i].x - mu) * rs * g.x + bb.x, o1 = (v[i].y - mu) * rs * g.y + bb.y;
                 float o2 = (v[i].z - mu) * rs * g.z + bb.z, o3 = (v[i].w - mu) * rs * g.w + bb.w;
                 if constexpr (OUT_F32) {
-                    LN_STORE(reinterpret_cast<f32x4*>((float*)u + (size_t)row * D) + c, (f32x4{o0, o1, o2, o3}));
+                    reinterpret_cast<f32x4*>((float*)u + (size_t)row * D)[c] = f32x4{o0, o1, o2, o3};
                 } else {
-                    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-                    const uint2 pk = pack4_bf16(o0, o1, o2, o3);
-                    LN_STORE(reinterpret_cast<u32x2*>((bf16_t*)u + (size_t)row * D) + c, (u32x2{pk.x, pk.y}));
+                    reinterpret_cast<uint2*>((bf16_t*)u + (size_t)row * D)[c] = pack4_bf16(o0, o1, o2, o3);
                 }
             }
         }
     };
     const int stride = gridDim.x * 4;
     int row = blockIdx.x * 4 + wave;
-#if DCV_LN_FWD_ROWS == 2
-    for (; row + stride < M; row += 2 * stride) {
-        f32x4 va[MAXV], vb[MAXV];
-        load_row(row, va);
-        load_row(row + stride, vb);
-        finish_row(row, va);
-        finish_row(row + stride, vb);
-    }
-#endif
     for (; row < M; row += stride) {
         f32x4 va[MAXV];
         load_row(row, va);
@@ -173,15 +152,13 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const void* __restrict__ du
             if (c < nv) {
                 f32x4 r = {rs * (g[i].x - m1 - xh[i].x * m2) + in.pin[i].x, rs * (g[i].y - m1 - xh[i].y * m2) + in.pin[i].y,
                            rs * (g[i].z - m1 - xh[i].z * m2) + in.pin[i].z, rs * (g[i].w - m1 - xh[i].w * m2) + in.pin[i].w};
-                LN_STORE(reinterpret_cast<f32x4*>(dx_out + (size_t)row * dx_row_stride) + c, r);
+                reinterpret_cast<f32x4*>(dx_out + (size_t)row * dx_row_stride)[c] = r;
                 if (dx_bf16) {
-                    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
                     if (bscale) {  // the copy feeds the residual branch below: DropPath's per-sample factor multiplies that branch's gradient
                         const float sc = bscale[row / rows_per_sample];
                         r.x *= sc; r.y *= sc; r.z *= sc; r.w *= sc;
                     }
-                    const uint2 pk = pack4_bf16(r.x, r.y, r.z, r.w);
-                    LN_STORE(reinterpret_cast<u32x2*>(dx_bf16 + (size_t)row * D) + c, (u32x2{pk.x, pk.y}));
+                    reinterpret_cast<uint2*>(dx_bf16 + (size_t)row * D)[c] = pack4_bf16(r.x, r.y, r.z, r.w);
                 }
             }
         }

@@ -562,9 +562,9 @@ class _BackwardScratch:
     """Where one backward's weight-gradient products run and the bf16 scratch they read: `self.<role>` is the current buffer of the roles
     dz, dxb and dqkv.  side None: one stream — the current stream is never asked for, nothing is recorded or waited for."""
 
-    def __init__(self, side, dev, wgrads, private, release, **buffers):
+    def __init__(self, side, dev, wgrads, private, **buffers):
         self.side_all, self.main = side, torch.cuda.current_stream(dev) if side is not None else None
-        self.wgrads, self.private_all, self.release = wgrads, private, release  # wgrads False: data-only backward, no weight-gradient GEMM
+        self.wgrads, self.private_all = wgrads, private  # wgrads False: data-only backward, no weight-gradient GEMM
         self.side, self.private, self.dxb_alt = None, False, None  # side, private: per block (begin_block)
         self.readers, self.held = {}, []  # id(buffer) -> the event after its last side-stream reader; what must outlive the side stream's work
         self.__dict__.update(buffers)
@@ -621,18 +621,10 @@ class _BackwardScratch:
         if self.side is not None:
             self.held.append(dict(L))
         L.clear()
-        if self.release or self.side is None:
-            # Everything in `held` — older layers' dz / dqkv / dxb and this layer's saved activations — has had its LAST reader queued
-            # (the block's weight-gradient launches — grouped or one by one, they are all in their queue by now).  On ONE stream that
-            # is enough to hand the memory back, and it is done (peak scratch = one layer instead of depth x 0.7 GB).  With the
-            # second stream the hand-back needs record_stream (the allocator reuses the block only after that stream's queued work), and
-            # that is OFF by default (DiChaViT.wgrad_scratch_release): measured in round 4, the deferred frees make the caching allocator
-            # fall into its slow path once every few dozen steps — ONE step of ~1000 ms among 35 ms steps in 2 of 3 runs — so the buffers
-            # are held until the streams join, as in round 3 (8.4 GB of scratch per backward for DiChaViT-S at bs 64, recycled step to step).
-            for t in self.held:
-                for v in (t.values() if isinstance(t, dict) else (t,)):
-                    if self.side is not None and torch.is_tensor(v) and v.is_cuda:
-                        v.record_stream(self.side)
+        if self.side is None:
+            # Everything in `held` — older layers' dz / dqkv / dxb — has had its LAST reader queued (the block's weight-gradient launches).  On ONE
+            # stream that is enough to hand the memory back (peak scratch = one layer instead of depth x 0.7 GB).  With the second stream the
+            # buffers are held until the streams join (8.4 GB of scratch per backward for DiChaViT-S at bs 64, recycled step to step).
             self.held.clear()
 
     def join(self):
@@ -686,7 +678,6 @@ class DiChaViT(nn.Module):
         self.attn_prescaled = os.environ.get("DCV_ATTN_PS", "1") != "0"
         self.fuse_ln_min_tiles = int(os.environ.get("DCV_FUSE_LN_MIN_TILES", "96"))  # 256-row tiles below which the fusion does not pay (_tokenise)
         self.fuse_ln_fwd = os.environ.get("DCV_FUSE_LN", "1") != "0"  # forward LayerNorm inside the residual GEMMs' epilogue (dcv_gemm_nt_resid_ln; D = 384)
-        self.wgrad_scratch_release = os.environ.get("DCV_WGRAD_RELEASE", "0") == "1"  # two streams: record_stream hand-back per layer (allocator stalls: see _BackwardScratch.end_block)
         self.wgrad_group = os.environ.get("DCV_WGRAD_GROUP", "1") != "0"  # a block's four weight gradients in one launch (needs the private scratch)
         self._group_cache = {}
         self._stats_w = {}
@@ -1353,8 +1344,7 @@ class DiChaViT(nn.Module):
         k0 = 0 if fk is None else fk
         Ms = M if k0 < len(fe.blocks) else 0  # fk == depth: only the final LayerNorm's backward (above) runs
         sc = _BackwardScratch(self._side_stream(dev) if self.wgrad_stream else None, dev, ga is not None, bool(self.wgrad_private_scratch),
-                              bool(self.wgrad_scratch_release), dxb=dxb, dz=torch.empty(Ms, 4 * D, dtype=bf, device=dev),
-                              dqkv=torch.empty(Ms, 3 * D, dtype=bf, device=dev))
+                              dxb=dxb, dz=torch.empty(Ms, 4 * D, dtype=bf, device=dev), dqkv=torch.empty(Ms, 3 * D, dtype=bf, device=dev))
         # what the blocks' backwards share; ps: the forward of this pass ran with pre-scaled q: qkv holds q', the backward entries must match
         b = types.SimpleNamespace(B=B, N=N, M=M, g=g, nt_kw=nt_kw, ps=bool(st.get("ps")), sc=sc,
                                   du=torch.empty(Ms, D, dtype=bf, device=dev), dO=torch.empty(Ms, D, dtype=bf, device=dev),

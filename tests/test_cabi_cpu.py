@@ -102,6 +102,45 @@ def test_gemm_tile_choice_rules():
     assert tn(200, 128, W) < 0 and tn(384, 384, W) == W and tn(384, 1536, N_) == N_
 
 
+def test_gemm_nt_ex_refuses_before_any_launch():
+    """dcv_gemm_nt_ex's answers for calls that must not reach a kernel, per epilogue and forced tile, from include/dcv.h: a missing buffer of the
+    epilogue is DCV_ERR_NULL (PATCH: DCV_ERR_SHAPE, with its table shapes), a combination without a kernel DCV_ERR_UNSUPPORTED, and the
+    weight-stationary kernel's 16-byte rule for out2 / aux / bias is looked at before the epilogue's buffers.  Every call here is refused, so
+    the made-up addresses are never read (the test runs with and without a device)."""
+    from diverse_channel_vit_amd import hip
+    lib = hip.load()
+    SHAPE, ALIGN, UNSUP, NULL = -1, -2, -3, -5
+    P, ODD = 0x10000, 0x10008  # 16-byte aligned, and not
+    NARROW, WIDE, PAIR, WS = hip.TILE_NARROW, hip.TILE_WIDE, hip.TILE_PAIR, hip.TILE_WS
+    BIAS, GELU, RESID, PLAIN, GELU_BWD, PATCH = (hip.EPI_BIAS_BF16, hip.EPI_BIAS_GELU_BF16, hip.EPI_BIAS_RESID_F32, hip.EPI_PLAIN_BF16,
+                                                hip.EPI_GELU_BWD_BF16, hip.EPI_PATCH)
+
+    def ex(epi, tile, M=64, N=384, K=384, bias=None, out2=None, aux=None, aux2=None, T=0, n=0, cap=0):
+        return lib.dcv_gemm_nt_ex(P, K, P, K, M, N, K, epi, bias, P, N, out2, N if out2 else 0, aux, N if aux else 0, aux2, T, n, cap, tile, None)
+
+    for tile in (NARROW, WIDE, PAIR, WS, hip.TILE_AUTO, hip.TILE_AUTO_WS):
+        assert ex(BIAS, tile) == NULL, tile
+        assert ex(GELU, tile, out2=P) == NULL and ex(GELU, tile, bias=P) == NULL, tile
+        assert ex(GELU_BWD, tile) == NULL and ex(GELU_BWD, tile, bias=P) == NULL, tile
+        assert ex(RESID, tile, aux=P) == (UNSUP if tile == WS else NULL), tile  # the fp32-output epilogue is not on the weight-stationary kernel
+        for epi in (-1, 6, 99):
+            assert ex(epi, tile, bias=P, out2=P, aux=P, aux2=P, T=64, n=32) == UNSUP, (epi, tile)
+    assert ex(PLAIN, hip.TILE_ALT) == UNSUP  # retired
+    # PATCH: on the 256 x 128 kernel only; bias, both tables, T rows per sample that divide M, n patches per channel that divide T
+    full = dict(bias=P, out2=P, aux=P, aux2=P, T=64, n=32)
+    for tile in (WIDE, PAIR, WS):
+        assert ex(PATCH, tile, **full) == UNSUP, tile
+    for miss in ("bias", "aux", "aux2"):
+        assert ex(PATCH, NARROW, **{**full, miss: None}) == SHAPE, miss
+    for T, n in ((0, 32), (64, 0), (48, 16), (64, 24)):
+        assert ex(PATCH, NARROW, **{**full, "T": T, "n": n}) == SHAPE, (T, n)
+    # weight-stationary: alignment before the epilogue's null checks; fewer workgroups than weight slices
+    assert ex(BIAS, WS, out2=ODD) == ALIGN and ex(GELU, WS, bias=ODD) == ALIGN and ex(GELU_BWD, WS, aux=ODD) == ALIGN
+    assert ex(GELU_BWD, NARROW, bias=ODD) == NULL  # the tiled kernels have no such rule: the missing aux is what they answer
+    assert ex(PLAIN, WS, N=1152, cap=2) == UNSUP
+    assert ex(BIAS, hip.TILE_AUTO_WS, M=9000, N=1152, cap=2) == NULL  # falls back to a tiled kernel, which then misses its bias
+
+
 def test_deterministic_workspace_sizes_and_switch():
     """The *_det_ws_floats entries are host logic (no GPU call): sizes for the headline step (256 CUs assumed without a device), and the
     package-level switch that selects the deterministic forms (default on; the reference sets cudnn.deterministic = True)."""

@@ -9,8 +9,8 @@ candidates alternating inside every round (median of --iters rounds), at B 64, n
 (a) must be faster than (b) — it moves a third of the bytes: the tool prints a line starting with DEFECT and exits with status 1 otherwise.
 Then get_intermediate_layers(n=4, pool="channel") and (n=4, pool=None) against one eval forward of DiChaViT-S at the headline config (8 channels,
 224 x 224, patch 16, bs 64).
-With --variants it also times variant builds of the kernel's launch plan (-DDCV_LP_TARGET_WGS=512: one workgroup per segment at the headline
-shape, no workspace, no second launch; -DDCV_LP_TWO_ROWS=1: two rows' loads in flight per wave), each in a child process.
+With --variants it also times a variant build of the kernel's launch plan (-DDCV_LP_TARGET_WGS=512: one workgroup per segment at the headline
+shape, no workspace, no second launch) in a child process.
 
     python tools/intermediate_layers_bench.py [--iters 50] [--variants]
 """
@@ -26,7 +26,7 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
 B, N_P, D = 64, 196, 384
-VARIANTS = {"lp_wg512": ["DCV_LP_TARGET_WGS=512"], "lp_two_rows": ["DCV_LP_TWO_ROWS=1"], "lp_wg512_two_rows": ["DCV_LP_TARGET_WGS=512", "DCV_LP_TWO_ROWS=1"]}
+VARIANTS = {"lp_wg512": ["DCV_LP_TARGET_WGS=512"]}
 
 
 def variant_lib(name):
