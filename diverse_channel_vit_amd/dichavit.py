@@ -429,7 +429,14 @@ class _EncoderFn(torch.autograd.Function):
        forward (no activation kept, the stream updated in place; same output bits) and the backward stops above block k: no tokeniser
        backward, dE and dpos are None.  k = depth is valid (only the final LayerNorm's backward runs).  Not with a DataParallel reducer.
        x gets a gradient when it requires one (dcv_patch_dgrad after the tokeniser's backward).  When only x does — no parameter, no E row,
-       no positional table, no DataParallel reducer — the backward is DATA-ONLY: no weight-gradient GEMM, no gradient arena, no saved Xp."""
+       no positional table, no DataParallel reducer — the backward is DATA-ONLY: no weight-gradient GEMM, no gradient arena, no saved Xp.
+       SELECTIVE BACKWARD: which parameter gradients the backward computes is one rule, the gradient plan (_grad_plan, from needs_input_grad).
+       Per linear layer (qkv, proj, fc1, fc2 of every block, the patch projection): weight asked -> its TN product as ever (dbias null when the
+       bias is not asked); bias asked alone -> dcv_bias_grad on the buffer the product would have read; neither -> nothing, and in the last two
+       cases the forward does not keep the product's other operand (h, u2, u1, Xp).  A block all four of whose weights are asked keeps its
+       grouped launch; one with fewer sends the products it has left one by one.  A parameter that did not ask gets None.  The full backward,
+       the frozen prefix and the data-only backward are corners of this rule.  With a DataParallel reducer attached the plan asks for
+       everything — the full backward runs as ever: the reducer's buckets expect every range."""
 
     @staticmethod
     def forward(ctx, model, ch_idx_dev, C, want_ortho, keep, tok, x, E, pos_tab, *params):
@@ -444,18 +451,18 @@ class _EncoderFn(torch.autograd.Function):
         """need: needs_input_grad as _EncoderFn.forward's arguments are numbered.  taps: None, or (blocks, pool) of _EncoderTapsFn."""
         # frozen prefix: nothing upstream of the first block k with a trainable parameter needs a gradient — not x, E, the positional table,
         # cls_token or the patch projection (need[6:12]), and by k's definition no parameter of a block below it (12 per block from need[12])
-        depth = len(model.feature_extractor.blocks)
-        frozen_k = _frozen_prefix(any(need[6:12]), [any(need[12 + 12 * bi:24 + 12 * bi]) for bi in range(depth)], any(need[12 + 12 * depth:]), model._dp)
+        plan = _grad_plan(need, len(model.feature_extractor.blocks), model._dp)
+        frozen_k = plan.frozen_k
         st = model._run_forward(x, ch_idx_dev, C, E, pos_tab, want_ortho, save=any(need), keep=keep,
                                 st_scale=model._cur_scale, st_shift=model._cur_shift, tok=tok, **({} if frozen_k is None else dict(frozen_k=frozen_k)),
-                                **({} if taps is None else dict(taps=taps)))
+                                **({} if taps is None else dict(taps=taps)),
+                                **({} if all(plan.params) else dict(gplan=plan)))  # everything asked (or a reducer attached): the full backward, as ever
         if need[6]:  # dcv_patch_dgrad's operands: the bf16 projection copy this forward multiplied by, the channel index, the input affine's scale
             fe = model.feature_extractor
             P = fe.patch_size
             st.update(dx_req=True, Wp=model._bf(fe.patch_embed.proj.weight), ch_idx=ch_idx_dev, in_scale=model._cur_scale, Ct=x.shape[1],
                       Hi=x.shape[2], Wi=x.shape[3], P=P)
-            if not any(need[7:]) and model._dp is None:  # data-only backward: no weight gradient, so the im2col rows are not kept
-                st.pop("Xp", None)
+            if plan.data_only:  # the plan with every entry "no / no" and nothing asked: the gradient arena is not touched
                 st["data_only"] = True
         ctx.model = model
         ctx.st = st
@@ -504,6 +511,31 @@ def _frozen_prefix(upstream: bool, blocks, norm: bool, dp) -> Optional[int]:
     if dp is not None or upstream or not (any(blocks) or norm):
         return None
     return next((bi for bi, b in enumerate(blocks) if b), len(blocks))
+
+
+_LINEARS = (("qkv", 2), ("proj", 4), ("fc1", 8), ("fc2", 10))  # a block's linear layers: name, place of the weight among the block's 12 parameters (the bias follows)
+
+
+def _grad_plan(need, depth: int, dp):
+    """The gradient plan of a forward, from `need`: needs_input_grad as _EncoderFn.forward's arguments are numbered (x 6, E 7, the positional table
+    8, then the encoder parameters in arena order from 9: cls_token, the patch projection's weight and bias, 12 per block, the final norm's two).
+      asked    per encoder parameter (arena order): did it ask for a gradient — what the backward node returns one for;
+      params   per encoder parameter: is its gradient computed.  asked, except under a DataParallel reducer (dp not None): all of them;
+      patch    (weight, bias) of the patch projection, from params;
+      blocks   per block {"qkv" | "proj" | "fc1" | "fc2": (weight, bias)}, from params.  Weight True: the TN product (with the bias sum when
+               bias is True); weight False, bias True: dcv_bias_grad; both False: nothing.  The forward keeps a product's X operand — h (fc2),
+               u2 (fc1), u1 (qkv), Xp (patch projection) — only when the weight is True;
+      frozen_k _frozen_prefix's answer;
+      data_only  nothing but x asked (and no reducer): every entry (False, False), no gradient arena.
+    The one rule behind _EncoderFn and DiChaViT._host_grad_plan."""
+    need = [bool(v) for v in need]
+    asked = tuple(need[9:])
+    assert len(asked) == 3 + 12 * depth + 2
+    params = asked if dp is None else (True,) * len(asked)
+    blocks = [{name: (params[3 + 12 * bi + o], params[3 + 12 * bi + o + 1]) for name, o in _LINEARS} for bi in range(depth)]
+    frozen_k = _frozen_prefix(any(need[6:12]), [any(need[12 + 12 * bi:24 + 12 * bi]) for bi in range(depth)], any(need[12 + 12 * depth:]), dp)
+    return types.SimpleNamespace(asked=asked, params=params, patch=(params[1], params[2]), blocks=blocks, frozen_k=frozen_k,
+                                 data_only=need[6] and not any(need[7:]) and dp is None)
 
 
 def _check_taps_above_prefix(tap_blocks, fk) -> None:
@@ -600,12 +632,18 @@ class _BackwardScratch:
         return torch.cuda.stream(self.side)
 
     def wgrad(self, Y, X, gw, gb):
-        """A weight-gradient product (Y: the scratch buffer it reads): launched now, or collected for the block's grouped launch."""
+        """A weight-gradient product (Y: the scratch buffer it reads): launched now, or collected for the block's grouped launch.  gw None
+        (the weight did not ask, X was not kept): the bias sum alone when gb is there (dcv_bias_grad, same stream, same bookkeeping), else nothing."""
+        if gw is None and gb is None:
+            return
         if self.plan:
             self.group.append((Y, X, gw, gb))
         elif self.wgrads:
             with self.on_side():
-                hip.gemm_tn_acc(Y, X, gw, gb)
+                if gw is None:
+                    hip.bias_grad(Y, gb)
+                else:
+                    hip.gemm_tn_acc(Y, X, gw, gb)
                 if self.side is not None:
                     done = torch.cuda.Event()
                     done.record(self.side)
@@ -844,6 +882,49 @@ class DiChaViT(nn.Module):
             elif lid <= depth:
                 p.requires_grad_(lid - 1 >= n_blocks)
         return self
+
+    def set_trainable(self, *specs: str) -> List[str]:
+        """Fine-tuning a chosen set of parameters: requires_grad becomes True on the union of `specs` and False on every other parameter; returns
+        the sorted names made trainable.  The backward then computes those gradients and no others (_EncoderFn, selective backward): a weight
+        that is not trained launches no weight-gradient GEMM and its forward operand is not kept.  Flags set by hand work the same way — the
+        backward reads the flags, not this method.  Specs:
+          "all"            every parameter;
+          "bias"           every *.bias — the linear layers', LayerNorm's beta, the head's, the patch projection's (BitFit);
+          "norm"           norm1 / norm2 of every block and the final norm, weight and bias;
+          "channel_embed"  patch_embed.channel_embed.weight, and patch_embed.channel_emb_proxies when the model has them: adapting to a new channel;
+          "tokeniser"      layer id 0 of `layer_id_of`;
+          "head"           layer id depth + 1 (final norm, classifier head, `proxies`, the learnable temperature);
+          anything else    an fnmatch pattern over the named_parameters() names.
+        A spec that matches nothing raises ValueError before any flag changes.  A channel embedding frozen by cfg.freeze_channel_emb stays frozen
+        (as in freeze_prefix), also when it is all a spec matches."""
+        import fnmatch
+        depth = len(self.feature_extractor.blocks)
+        named = list(self.named_parameters())
+        ce = "feature_extractor.patch_embed.channel_embed.weight"
+        presets = {
+            "all": lambda n: True,
+            "bias": lambda n: n.endswith(".bias"),
+            "norm": lambda n: n.startswith("feature_extractor.norm.") or ".norm1." in n or ".norm2." in n,
+            "channel_embed": lambda n: n in (ce, "feature_extractor.patch_embed.channel_emb_proxies"),
+            "tokeniser": lambda n: layer_id_of(n, depth) == 0,
+            "head": lambda n: layer_id_of(n, depth) == depth + 1,
+        }
+        chosen = set()
+        for spec in specs:
+            if not isinstance(spec, str):
+                raise ValueError(f"set_trainable: specs are strings, got {spec!r}")
+            match = presets.get(spec, lambda n, _s=spec: fnmatch.fnmatchcase(n, _s))
+            hit = {n for n, _ in named if match(n)}
+            if not hit:
+                raise ValueError(f"set_trainable: {spec!r} matches no parameter")
+            chosen |= hit
+        if not specs:
+            raise ValueError("set_trainable: name at least one spec ('all', 'bias', 'norm', 'channel_embed', 'tokeniser', 'head' or a pattern)")
+        if _cfg_get(self.cfg, "freeze_channel_emb", False):
+            chosen.discard(ce)
+        for n, p in named:
+            p.requires_grad_(n in chosen)
+        return sorted(chosen)
 
     # ---------------------------------------------------------------------------------------
     # host-side pieces of PatchEmbedPerChannel.forward (dichavit.py:110-417)
@@ -1126,9 +1207,10 @@ class DiChaViT(nn.Module):
         hip.attn_fwd(qkv, o, lse, B, N, H, D // H, _ATTN_SCALE, prescaled=f.ps, **({} if nq is None else dict(nq=nq)))
         return dict(u1=u1, mean1=mean1, rstd1=rstd1, qkv=qkv, o=o, lse=lse)
 
-    def _block_residuals(self, f, bi, xcur, a, sv=False, tail=False):
+    def _block_residuals(self, f, bi, xcur, a, sv=False, tail=False, xops=None):
         """Second half of encoder block bi, after the attention `a` (_block_attention): attn.proj + residual, norm2, MLP, fc2 + residual.  sv: the
         activations are kept for the backward (the stream goes to fresh buffers, otherwise it is updated in place).  tail: the CLS rows only.
+        xops: the block's entry of the gradient plan (_grad_plan): u1, u2 and h are kept only for a weight gradient that is asked for (None: all).
         Returns (the stream after the block, the next block's norm1 if it came out of the fc2 epilogue else None, the block's saved state)."""
         fe = self.feature_extractor
         blk, nxt = fe.blocks[bi], fe.blocks[bi + 1] if bi + 1 < len(fe.blocks) else None
@@ -1179,11 +1261,15 @@ class DiChaViT(nn.Module):
             hip.gemm_nt(hact, wb(blk.mlp.fc2.weight), hip.EPI_BIAS_RESID_F32, xout, bias=blk.mlp.fc2.bias, aux=xmid,
                         **(dict(aux2=dsc[1], T=R // B) if dsc else {}))
         kept = dict(x_in=xcur, **a, x_mid=xmid, u2=u2, mean2=mean2, rstd2=rstd2, z=z, h=hact, tail=tail, o_c=o_c) if sv else {}
+        if sv and xops is not None:
+            for key, lin in (("u1", "qkv"), ("u2", "fc1"), ("h", "fc2")):
+                if not xops[lin][0]:
+                    del kept[key]
         return xout, pre_ln, dict(drop=dsc, **kept)  # the DropPath factors: all that the block above reads from a block that is not kept
 
-    def _block_forward(self, f, bi, xcur, pre_ln, sv=False, tail=False):
+    def _block_forward(self, f, bi, xcur, pre_ln, sv=False, tail=False, xops=None):
         """Encoder block bi on every row, or as the CLS-only tail: the CLS query and, after the attention, the CLS rows alone."""
-        return self._block_residuals(f, bi, xcur, self._block_attention(f, bi, xcur, pre_ln, nq=1 if tail else None), sv, tail)
+        return self._block_residuals(f, bi, xcur, self._block_attention(f, bi, xcur, pre_ln, nq=1 if tail else None), sv, tail, xops)
 
     def _final_norm(self, f, xcur, row_stride):
         """The final LayerNorm on the CLS rows only (dichavit.py:651-652): (feature [B, D], mean, rstd)."""
@@ -1224,11 +1310,13 @@ class DiChaViT(nn.Module):
             hip.ln_bwd(dtap.view(B * N, D), x, stats[0], stats[1], fe.norm.weight, dx, dx, None, gw, gb, B * N, D)
 
     def _run_forward(self, x, ch_idx_dev, C, E, pos_tab, want_ortho, save, keep=None, st_scale=None, st_shift=None, tok=None, frozen_k=None,
-                     refresh=True, taps=None):
+                     refresh=True, taps=None, gplan=None):
         """The training / eval forward: operand copies, tokeniser, blocks, final norm.  Returns the state: feat, stats and, with save, what the
         backward reads.  frozen_k=k (with save): blocks < k and the tokeniser keep nothing for the backward (they run as with save=False, on
         the same kernels); st["layers"] still has one entry per block — the backward indexes it by block number — which for blocks < k holds
         the DropPath factors only.  refresh=False: the operand copies are the caller's business (_probe_relevance).
+        gplan (with save): the gradient plan (_grad_plan), kept as st["gplan"]: the X operand of a weight gradient nobody asked for — h, u2, u1 of
+        a block, the tokeniser's Xp — is not kept (the launches are the same).  None: everything is kept.
         taps=(blocks, pool) (forward_with_features): st["tap_out"] lists the final norm of the stream after each listed block, launched right
         after that block; the last block leaves its CLS-only form when it is tapped with a pool other than "cls".  With save, st["taps"] keeps
         what their backward reads: the streams themselves — block l + 1's saved x_in, x_final for the last block: no copy — and the row
@@ -1238,9 +1326,12 @@ class DiChaViT(nn.Module):
             self._refresh_operand_copies(stochastic=bool(save) and self.training and self.stochastic_weight_rounding, prescale_q=bool(self.attn_prescaled))
         f, xcur, stats, kept = self._tokenise(x, ch_idx_dev, C, E, pos_tab, want_ortho, keep, st_scale, st_shift, tok)
         fk = frozen_k if save else None
-        st = dict(B=f.B, C=C, n=f.n, N=f.N, M=f.M, save=save, tok=f.tok, ps=f.ps, frozen_k=fk)
+        gplan = gplan if save else None
+        st = dict(B=f.B, C=C, n=f.n, N=f.N, M=f.M, save=save, tok=f.tok, ps=f.ps, frozen_k=fk, gplan=gplan)
         if save and fk is None:
             st.update(kept)
+            if gplan is not None and not gplan.patch[0]:
+                del st["Xp"]
         layers, pre_ln = [], None
         tap_blocks, tap_pool = taps if taps is not None else ((), None)
         _check_taps_above_prefix(tap_blocks, fk)  # fk from needs_input_grad: the host check of forward_with_features saw requires_grad flags only
@@ -1249,7 +1340,7 @@ class DiChaViT(nn.Module):
         for bi in range(depth):
             sv = save and (fk is None or bi >= fk)  # this block's activations are kept for the backward
             tail = self.cls_only_tail and bi == depth - 1 and not full_last  # last block on the CLS rows only: it hands over compact CLS rows
-            xcur, pre_ln, L = self._block_forward(f, bi, xcur, pre_ln, sv, tail)
+            xcur, pre_ln, L = self._block_forward(f, bi, xcur, pre_ln, sv, tail, gplan.blocks[bi] if gplan is not None else None)
             layers.append(L)
             if bi in tap_blocks:
                 cap, tstats = self._tap_forward(f, xcur, tap_pool, tail, save)
@@ -1276,15 +1367,19 @@ class DiChaViT(nn.Module):
         state (st["data_only"]: nothing but x needs a gradient): the gradient arena is not touched, LayerNorm's dgamma / dbeta and d(cls) go to
         throwaway scratch and no weight-gradient GEMM is launched."""
         dp = self._dp
+        fe = self.feature_extractor
+        # Where a gradient nobody asked for goes.  LayerNorm's dgamma / dbeta and d(cls) come out of kernels that have no form without them
+        # (dcv_ln_bwd, dcv_patch_bwd): throwaway scratch.  Every other parameter: None — its product is not launched (_BackwardScratch.wgrad).
+        junk = torch.empty(2, self.dim, dtype=torch.float32, device=dfeat.device)
+        norms = [fe.norm] + [n for b in fe.blocks for n in (b.norm1, b.norm2)]
+        junk_row = {id(fe.cls_token): 0, **{id(n.weight): 0 for n in norms}, **{id(n.bias): 1 for n in norms}}
+        unasked = lambda p: junk[junk_row[id(p)]].view(p.shape) if id(p) in junk_row else None  # noqa: E731
         if st.get("data_only"):
-            fe = self.feature_extractor
-            junk = torch.empty(2, self.dim, dtype=torch.float32, device=dfeat.device)
-            biases = {id(fe.norm.bias)} | {id(b.norm1.bias) for b in fe.blocks} | {id(b.norm2.bias) for b in fe.blocks}
-            # only LayerNorm's and d(cls) slots are written; the weight-gradient slots are requested but never launched
-            g = lambda p: junk[1 if id(p) in biases else 0].view(p.shape) if p.numel() == self.dim else None  # noqa: E731
-            return self._run_backward_body(st, dfeat, dstats, None, g, None, {})
+            return self._run_backward_body(st, dfeat, dstats, None, unasked, None, {})
         ga = self._new_grad_arena()
-        g = lambda p: self._gview(ga, p)  # noqa: E731
+        plan = st.get("gplan")
+        wanted = None if plan is None else {id(p) for p, w in zip(self._enc_params, plan.params) if w}
+        g = lambda p: self._gview(ga, p) if wanted is None or id(p) in wanted else unasked(p)  # noqa: E731
         # Data parallel: RCCL's all-reduce kernels run beside this backward, one workgroup per channel with 21 KB of LDS each
         # (read from librccl's gfx950 code object).  Neither NT GEMM kernel can share a CU with one (144 KB / 160 KB of the 160),
         # and both deal their tiles statically to one workgroup per CU, so a workgroup whose CU is taken starts late and the
@@ -1370,7 +1465,7 @@ class DiChaViT(nn.Module):
         if b.probe is not None:  # an inspection call: the walk ends above block k0, no gradient leaves
             return None, None, []
         if fk is not None:
-            return None, None, [self._gview(ga, p) if p.requires_grad else None for p in self._enc_params]
+            return None, None, self._asked_grads(st, ga)
         return self._tokeniser_backward(st, dx, dstats, ga, g, dp)
 
     def _block_backward(self, b, li, L, dx, below):
@@ -1384,16 +1479,19 @@ class DiChaViT(nn.Module):
         sc.begin_block(tail)
         # wgrad_group (with private scratch): a block's four weight-gradient products go out as ONE launch (dcv_gemm_tn_group) once the last of
         # their operands (dqkv) exists: the tiles of all four fill the CUs, so each is split 7 ways over the token rows instead of 21-85 ways
-        if sc.private and self.wgrad_group and sc.wgrads:
+        # ... when all four weights asked for their gradient (_grad_plan); a block with fewer sends what it has left one by one (gemm_tn_acc, the
+        # form wgrad_group = False uses: every surviving product keeps the bits of an existing launch form)
+        if sc.private and self.wgrad_group and sc.wgrads and all(g(w) is not None for w in (blk.mlp.fc2.weight, blk.mlp.fc1.weight, blk.attn.proj.weight,
+                                                                                           blk.attn.qkv.weight)):
             sc.plan = self._group_ok(M, D)
         du_ = b.du[:R] if tail else b.du
         # MLP
         dxb, dz = sc.dxb, sc.fresh("dz")
         dz_ = dz[:R] if tail else dz
         hip.gemm_nt(dxb, self._bf(blk.mlp.fc2.weight, True), hip.EPI_GELU_BWD_BF16, dz_, aux=L["z"], **nt_kw)
-        sc.wgrad(dxb, L["h"], g(blk.mlp.fc2.weight), g(blk.mlp.fc2.bias))
+        sc.wgrad(dxb, L.get("h"), g(blk.mlp.fc2.weight), g(blk.mlp.fc2.bias))
         hip.gemm_nt(dz_, self._bf(blk.mlp.fc1.weight, True), hip.EPI_PLAIN_BF16, du_, **nt_kw)
-        sc.wgrad(dz_, L["u2"], g(blk.mlp.fc1.weight), g(blk.mlp.fc1.bias))
+        sc.wgrad(dz_, L.get("u2"), g(blk.mlp.fc1.weight), g(blk.mlp.fc1.bias))
         dxb = sc.fresh("dxb")
         dsc = L.get("drop")  # this block's (attention, MLP) DropPath factors: the copy written here feeds its attention branch
         hip.ln_bwd(du_, L["x_mid"], L["mean2"], L["rstd2"], blk.norm2.weight, dx, dx, dxb, g(blk.norm2.weight), g(blk.norm2.bias), R, D,
@@ -1402,8 +1500,7 @@ class DiChaViT(nn.Module):
         if tail:
             dO_c = b.du[B:2 * B]  # scratch rows of the same buffer
             hip.gemm_nt(dxb, self._bf(blk.attn.proj.weight, True), hip.EPI_PLAIN_BF16, dO_c, **nt_kw)
-            if sc.wgrads:
-                hip.gemm_tn_acc(dxb, L["o_c"], g(blk.attn.proj.weight), g(blk.attn.proj.bias))
+            sc.wgrad(dxb, L["o_c"], g(blk.attn.proj.weight), g(blk.attn.proj.bias))  # the tail has no side stream and no group: launched here
             b.dO.view(B, N, D)[:, 0].copy_(dO_c)  # only the CLS rows of dO are read (nq = 1)
             if b.probe is not None:
                 b.probe(L, b)
@@ -1418,7 +1515,7 @@ class DiChaViT(nn.Module):
             sc.wgrad(dxb, L["o"], g(blk.attn.proj.weight), g(blk.attn.proj.bias))
             hip.attn_bwd(L["qkv"], L["o"], b.dO, L["lse"], b.delta, sc.fresh("dqkv"), B, N, H, D // H, _ATTN_SCALE, prescaled=b.ps)
         hip.gemm_nt(sc.dqkv, self._bf(blk.attn.qkv.weight, True), hip.EPI_PLAIN_BF16, b.du, **nt_kw)
-        sc.wgrad(sc.dqkv, L["u1"], g(blk.attn.qkv.weight), g(blk.attn.qkv.bias))
+        sc.wgrad(sc.dqkv, L.get("u1"), g(blk.attn.qkv.weight), g(blk.attn.qkv.bias))
         sc.launch_group()
         if li - 1 in b.dtaps:
             # the tap on the stream this block read (block li - 1's output, L["x_in"]): its gradient joins dx after norm2's backward — the copy
@@ -1461,12 +1558,25 @@ class DiChaViT(nn.Module):
             dxin = torch.empty(B, st["Ct"], st["Hi"], st["Wi"], dtype=f32, device=dev)
             hip.patch_dgrad(dYb, st["Wp"], st["ch_idx"], dxin, B, st["Ct"], C, st["Hi"], st["Wi"], st["P"], scale=st["in_scale"])
             st["dx_out"] = dxin
-        if wgrads:
-            hip.gemm_tn_acc(dYb, st["Xp"], g(pe.proj.weight), g(pe.proj.bias))
+        if wgrads:  # the patch projection follows the plan's table like a block's layers
+            gw, gb = g(pe.proj.weight), g(pe.proj.bias)
+            if gw is not None:
+                hip.gemm_tn_acc(dYb, st["Xp"], gw, gb)
+            elif gb is not None:
+                hip.bias_grad(dYb, gb)
         if dp is not None:
             dp.grad_ready(ga, *self._range_of([fe.cls_token, pe.proj.bias]))
             dp.flush()
-        return dE, dpos, [self._gview(ga, p) if (wgrads and p.requires_grad) else None for p in self._enc_params]
+        return dE, dpos, self._asked_grads(st, ga)
+
+    def _asked_grads(self, st, ga):
+        """What the backward node returns for the encoder parameters: the arena view of every parameter that asked (the gradient plan), None for
+        the others."""
+        if ga is None:
+            return [None] * len(self._enc_params)
+        plan = st.get("gplan")
+        asked = [p.requires_grad for p in self._enc_params] if plan is None else plan.asked
+        return [self._gview(ga, p) if a else None for p, a in zip(self._enc_params, asked)]
 
     def _group_ok(self, M, D):
         """How a block's four weight-gradient products (in the order the backward produces their operands: fc2, fc1, proj, qkv) are grouped
@@ -1545,14 +1655,19 @@ class DiChaViT(nn.Module):
     def _host_frozen_prefix(self, x) -> Optional[int]:
         """_frozen_prefix as _EncoderFn will find it for a forward of x, from requires_grad flags alone (no device work): upstream of the blocks are
         x and what the node's E, pos_tab, cls_token and patch-projection inputs come from."""
+        plan = self._host_grad_plan(x)
+        return None if plan is None else plan.frozen_k
+
+    def _host_grad_plan(self, x=None):
+        """_grad_plan as _EncoderFn will find it for a forward of x, from requires_grad flags alone (no device work); None when no graph is
+        recorded.  The node's E input comes from channel_embed, its positional table from pos_embed."""
         if not torch.is_grad_enabled():
             return None
         fe = self.feature_extractor
         pe = fe.patch_embed
-        up = [fe.cls_token, fe.pos_embed, pe.proj.weight, pe.proj.bias] + ([pe.channel_embed.weight] if hasattr(pe, "channel_embed") else [])
-        upstream = (torch.is_tensor(x) and x.requires_grad) or any(p.requires_grad for p in up)
-        return _frozen_prefix(upstream, [any(p.requires_grad for p in blk.parameters()) for blk in fe.blocks],
-                              any(p.requires_grad for p in fe.norm.parameters()), self._dp)
+        need = [False] * 6 + [torch.is_tensor(x) and x.requires_grad, hasattr(pe, "channel_embed") and pe.channel_embed.weight.requires_grad,
+                              fe.pos_embed.requires_grad] + [p.requires_grad for p in self._enc_param_list()]
+        return _grad_plan(need, len(fe.blocks), self._dp)
 
     def _forward_impl(self, x: torch.Tensor, chunk_name: str, training_chunks: Optional[str] = None, init_first_layer=None,
                       new_channel_init=None, taps=None, **kwargs):

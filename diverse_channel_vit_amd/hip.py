@@ -31,6 +31,9 @@ _SIGS = {
     "dcv_gemm_tn_acc_det": ([_vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _l, _vp], _i),
     "dcv_gemm_tn_group_ws_floats": ([_vp, _i, _i], _l),
     "dcv_gemm_tn_group": ([_vp, _i, _i, _vp, _l, _vp], _i),
+    "dcv_bias_grad_ws_floats": ([_i, _i], _l),
+    "dcv_bias_grad": ([_vp, _i, _i, _i, _vp, _vp, _l, _vp], _i),
+    "dcv_bias_grad_plan": ([_i, _i, _vp, _vp, _vp, _vp, _vp], _i),
     "dcv_ln_fwd": ([_vp, _l, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _f, _vp], _i),
     "dcv_ln_pool_channels_ws_floats": ([_i, _i, _i, _i], _l),
     "dcv_ln_pool_channels": ([_vp, _vp, _vp, _f, _vp, _i, _i, _i, _i, _vp, _l, _vp], _i),
@@ -345,6 +348,30 @@ def gemm_tn_acc(Y, X, dW, dbias=None, tile=TILE_AUTO, ws=None):
             _req(ws, torch.float32, "ws")
             rc = lib.dcv_gemm_tn_acc_det(_p(Y), P, _p(X), Q, M, P, Q, _p(dW), Q, _p(dbias), tile, _p(ws), ws.numel(), _stream())
     _check(rc, "dcv_gemm_tn_acc")
+
+
+def bias_grad_ws_floats(M, P) -> int:
+    return _ws_size(load().dcv_bias_grad_ws_floats(M, P))
+
+
+def bias_grad(Y, dbias, ws=None):
+    """dbias[P] += colsum(Y[M,P]) — gemm_tn_acc's bias gradient without the product (include/dcv.h: dcv_bias_grad), for a Linear whose bias
+    is trained and whose weight is frozen.  Y: bf16 [M, P], rows Y.stride(0) >= P apart.  Always the deterministic form: the kernel has no
+    other.  ws: the caller's workspace of >= bias_grad_ws_floats(M, P) floats (tests); by default the stream's shared one."""
+    if not Y.is_cuda or Y.dtype != torch.bfloat16 or Y.dim() != 2 or Y.stride(1) != 1:
+        raise RuntimeError("Y: expected a bf16 [M, P] GPU tensor with unit column stride")
+    _req(dbias, torch.float32, "dbias")
+    M, P = Y.shape
+    if dbias.numel() != P:
+        raise ValueError("bias_grad: dbias holds P floats")
+    lib = load()
+    if ws is None:
+        ws = _workspace(_ws_size(lib.dcv_bias_grad_ws_floats(M, P)), dbias)
+    else:
+        _req(ws, torch.float32, "ws")
+    with _timer(lambda: ("bias_grad_kernel", f"M{M} P{P}", 0.0, None, 2.0 * M * P)):
+        rc = lib.dcv_bias_grad(_p(Y), Y.stride(0), M, P, _p(dbias), _p(ws), ws.numel(), _stream())
+    _check(rc, "dcv_bias_grad")
 
 
 def ln_fwd(x, gamma, beta, out, mean, rstd, M, D, eps, x_row_stride=None):

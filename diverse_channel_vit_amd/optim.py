@@ -305,8 +305,8 @@ def clip_grad_norm_(model, max_norm: float) -> torch.Tensor:
     seen = set()
     if ga is not None:
         # merged runs of arena-resident gradients (slot padding included: it holds zeros): one run when every encoder parameter has its
-        # gradient there, two with a frozen prefix.  The slot of a parameter WITHOUT .grad stays out: a frozen weight that is not part of
-        # a prefix still has its gradient computed into the arena.
+        # gradient there, two with a frozen prefix, one per run of trainable tensors under set_trainable().  The slot of a parameter WITHOUT
+        # .grad stays out (under a DataParallel reducer a frozen weight still has its gradient computed into the arena).
         offs, total = model._enc_off, model._enc_size
         start = end = None
         for i, (p, o) in enumerate(zip(enc, offs)):

@@ -119,6 +119,20 @@ typedef struct dcv_tn_item {
 long dcv_gemm_tn_group_ws_floats(const dcv_tn_item* items, int n, int M);
 int dcv_gemm_tn_group(const dcv_tn_item* items, int n, int M, float* ws, long ws_floats, void* stream);
 
+/* The bias gradient alone (a Linear whose bias is trained and whose weight is frozen): dbias[P] (f32) += sum_m Y[m,P], Y bf16 [M,P] with row
+ * stride ldy — the semantics of dcv_gemm_tn_acc's dbias argument without the product.  ALWAYS deterministic (no atomic form): per-workgroup
+ * partial sums through ws (at least dcv_bias_grad_ws_floats(M, P) floats, contents irrelevant before and after), added to dbias in workgroup
+ * order by a second launch; fp32 accumulation.  One streaming pass over Y in 16-byte loads.  Checked in this order, before any HIP call:
+ * Y / dbias / ws NULL -> DCV_ERR_NULL; M < 1, P < 1 or ldy < P -> DCV_ERR_SHAPE; Y, dbias or ws not 16-byte aligned, ldy % 8 != 0 ->
+ * DCV_ERR_ALIGN; P % 8 != 0 -> DCV_ERR_UNSUPPORTED, as is a row chunk (rows_per_wg rows of ldy elements) of 2 GB or more; ws_floats too small
+ * -> DCV_ERR_SHAPE. */
+long dcv_bias_grad_ws_floats(int M, int P);
+int dcv_bias_grad(const void* Y, int ldy, int M, int P, float* dbias, float* ws, long ws_floats, void* stream);
+/* its launch plan — host logic, no GPU call: the P / 8 16-byte units of a row fall into col_chunks column chunks of at most 64 lanes; one wave
+ * step takes rows_per_wave rows of its chunk (8 loads in flight), a workgroup of four waves rows_per_wg; the grid is row_wgs x col_chunks
+ * workgroups, capped at 512, and a workgroup walks at most `passes` row chunks (1 below the cap).  ws holds row_wgs * P floats. */
+int dcv_bias_grad_plan(int M, int P, int* col_chunks, int* rows_per_wave, int* rows_per_wg, int* row_wgs, int* passes);
+
 /* LayerNorm (eps inside the sqrt, biased variance) — vit.py:361,374 / dichavit.py:651.
  * out is bf16 [M,D] (or f32 when out_is_f32); mean/rstd [M] may be NULL. x rows are x_row_stride floats apart. */
 int dcv_ln_fwd(const float* x, long x_row_stride, const float* gamma, const float* beta, void* out, int out_is_f32, float* mean,
