@@ -732,6 +732,7 @@ class DiChaViT(nn.Module):
         # master every step), round-to-nearest otherwise.  DCV_WEIGHT_ROUNDING=nearest turns it off.
         self.stochastic_weight_rounding = os.environ.get("DCV_WEIGHT_ROUNDING", "stochastic") != "nearest"
         self._sr_seed = None  # device int32 word, bumped after every stochastically rounded refresh
+        self._copies_held = 0  # inside forward_views: its number of views — the operand copies were refreshed once for all its forwards
         # last block on the CLS rows only (exact: the encoder output is norm(x)[:, 0]); DCV_CLS_TAIL=0 computes every row
         self.cls_only_tail = os.environ.get("DCV_CLS_TAIL", "1") != "0"
 
@@ -1314,7 +1315,8 @@ class DiChaViT(nn.Module):
         """The training / eval forward: operand copies, tokeniser, blocks, final norm.  Returns the state: feat, stats and, with save, what the
         backward reads.  frozen_k=k (with save): blocks < k and the tokeniser keep nothing for the backward (they run as with save=False, on
         the same kernels); st["layers"] still has one entry per block — the backward indexes it by block number — which for blocks < k holds
-        the DropPath factors only.  refresh=False: the operand copies are the caller's business (_probe_relevance).
+        the DropPath factors only.  refresh=False: the operand copies are the caller's business (_probe_relevance); inside forward_views they
+        are its business too (_copies_held).
         gplan (with save): the gradient plan (_grad_plan), kept as st["gplan"]: the X operand of a weight gradient nobody asked for — h, u2, u1 of
         a block, the tokeniser's Xp — is not kept (the launches are the same).  None: everything is kept.
         taps=(blocks, pool) (forward_with_features): st["tap_out"] lists the final norm of the stream after each listed block, launched right
@@ -1322,12 +1324,14 @@ class DiChaViT(nn.Module):
         what their backward reads: the streams themselves — block l + 1's saved x_in, x_final for the last block: no copy — and the row
         statistics of the pools that go through dcv_ln_bwd."""
         depth = len(self.feature_extractor.blocks)
-        if refresh:
+        if refresh and not self._copies_held:
             self._refresh_operand_copies(stochastic=bool(save) and self.training and self.stochastic_weight_rounding, prescale_q=bool(self.attn_prescaled))
         f, xcur, stats, kept = self._tokenise(x, ch_idx_dev, C, E, pos_tab, want_ortho, keep, st_scale, st_shift, tok)
         fk = frozen_k if save else None
         gplan = gplan if save else None
         st = dict(B=f.B, C=C, n=f.n, N=f.N, M=f.M, save=save, tok=f.tok, ps=f.ps, frozen_k=fk, gplan=gplan)
+        if save and self._copies_held > 1:
+            st["private_grads"] = True  # one of several nodes that meet in ONE backward (forward_views): _asked_grads
         if save and fk is None:
             st.update(kept)
             if gplan is not None and not gplan.patch[0]:
@@ -1574,6 +1578,13 @@ class DiChaViT(nn.Module):
         the others."""
         if ga is None:
             return [None] * len(self._enc_params)
+        if st.get("private_grads"):
+            # Several nodes of one forward_views call run in ONE backward, and autograd adds a parameter's gradients only after the last of them
+            # has delivered: until then .grad is unset, _new_grad_arena finds the arena free, and the next node would zero and overwrite the
+            # buffer the earlier node's views still name (the sum of aliases: twice the last node's gradient).  Each such node hands over a copy
+            # that nothing else names.  The price: one flat copy per view, and .grad no longer lives in the arena (HipAdamW and clip_grad_norm_
+            # take their per-parameter paths).  A single forward per backward keeps the arena views, as ever.
+            ga = ga.clone()
         plan = st.get("gplan")
         asked = [p.requires_grad for p in self._enc_params] if plan is None else plan.asked
         return [self._gview(ga, p) if a else None for p, a in zip(self._enc_params, asked)]
@@ -1651,6 +1662,55 @@ class DiChaViT(nn.Module):
         _check_taps_above_prefix(blocks, self._host_frozen_prefix(x))
         with torch.autocast(device_type="cuda", enabled=False):
             return self._forward_impl(x, chunk_name, training_chunks, init_first_layer, new_channel_init, taps=(blocks, pool), **kwargs)
+
+    def forward_views(self, views, chunk_name: str, training_chunks: Optional[str] = None, *, pool="cls", **kwargs):
+        """Several forwards under ONE set of bf16 operand copies (multi-crop self-distillation: ssl.DINOLoss).  views: a sequence of image batches,
+        e.g. [x_global (2B, 224 x 224), x_local (8B, 96 x 96)]; each runs as forward_with_features(x, chunk_name, training_chunks, layers=1,
+        pool="cls", ...) runs it — its own _EncoderFn node and saved state, its own HCS and DropPath draws, the positional table resampled to its
+        resolution — except that the operand copies are refreshed once, before the first: one rounding draw and one _sr_seed bump per call with
+        stochastic rounding on.  Returns (feats, extra): the CLS features after the final norm, concatenated in view order [sum of the batches, D],
+        fp32 and connected to the graph, and the sum of the views' regularisers (a zero scalar in eval mode).
+        Why it exists: an encoder node's backward multiplies by the LIVE operand copies.  Two plain forwards before one backward leave the first
+        node with the second's copies — other weight bits under stochastic rounding.  Here every node of the call finds the copies its forward
+        used, as long as the backward runs before the next training forward of this model.  Backward order is autograd's.  With more than one view
+        every node hands autograd a private copy of its parameter gradients (they meet in one backward, where the shared gradient arena cannot
+        be told free from in use); .grad is their sum and does not live in the arena, so HipAdamW takes its per-parameter path for that step.  The classifier head's output is not returned (its parameters receive no
+        gradient from this call: freeze them or leave them out of the optimiser).
+        Not supported: a DataParallel reducer (NotImplementedError: its begin_forward() assumes one forward per backward), GraphedTrainStep, a
+        pool other than "cls"."""
+        if pool != "cls":
+            raise ValueError(f"pool={pool!r}: forward_views returns CLS features (pool='cls')")
+        views = list(views)
+        if not views:
+            raise ValueError("forward_views: no views")
+        for x in views:
+            self._check_input(x)
+        if self._dp is not None:
+            raise NotImplementedError("forward_views with a DataParallel reducer attached: the reducer's begin_forward() assumes one forward per "
+                                      "backward")
+        if self._copies_held:
+            raise RuntimeError("forward_views: already inside a forward_views call of this model")
+        self._ensure_arena(views[0].device)
+        fe = self.feature_extractor
+        pe = fe.patch_embed
+        # will the nodes save for a backward (_EncoderFn: any(needs_input_grad)), from requires_grad flags alone, as _host_grad_plan reads them
+        save = torch.is_grad_enabled() and (any(x.requires_grad for x in views) or fe.pos_embed.requires_grad or
+                                            (hasattr(pe, "channel_embed") and pe.channel_embed.weight.requires_grad) or
+                                            any(p.requires_grad for p in self._enc_param_list()))
+        with torch.autocast(device_type="cuda", enabled=False):
+            self._refresh_operand_copies(stochastic=save and self.training and self.stochastic_weight_rounding, prescale_q=bool(self.attn_prescaled))
+        self._copies_held = len(views)
+        try:
+            feats, extra = [], None
+            for x in views:
+                out, taps = self.forward_with_features(x, chunk_name, training_chunks, layers=1, pool="cls", **kwargs)
+                feats.append(taps[0])
+                if self.training:
+                    extra = out[1] if extra is None else extra + out[1]
+        finally:
+            self._copies_held = 0
+        feats = torch.cat(feats, dim=0)
+        return feats, (extra if extra is not None else feats.new_zeros(()))
 
     def _host_frozen_prefix(self, x) -> Optional[int]:
         """_frozen_prefix as _EncoderFn will find it for a forward of x, from requires_grad flags alone (no device work): upstream of the blocks are

@@ -82,6 +82,10 @@ _SIGS = {
     "dcv_ortho_bwd": ([_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp], _i),
     "dcv_proxy_loss_supported": ([_i, _i], _i),
     "dcv_proxy_loss": ([_vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp], _i),
+    "dcv_dino_loss_ws_floats": ([_i, _i, _i], _l),
+    "dcv_dino_loss_fwd": ([_vp, _l, _vp, _l, _vp, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _l, _vp], _i),
+    "dcv_dino_loss_bwd": ([_vp, _l, _vp, _l, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _vp, _l, _vp], _i),
+    "dcv_dino_loss_plan": ([_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i),
     "dcv_adamw": ([_vp, _vp, _vp, _vp, _l, _f, _f, _f, _f, _f, _i, _f, _vp], _i),
     "dcv_adamw_dyn": ([_vp, _vp, _vp, _vp, _l, _vp, _vp], _i),
     "dcv_adamw_set_hyper": ([_vp, _f, _f, _f, _f, _f, _i, _f, _vp], _i),
@@ -372,6 +376,74 @@ def bias_grad(Y, dbias, ws=None):
     with _timer(lambda: ("bias_grad_kernel", f"M{M} P{P}", 0.0, None, 2.0 * M * P)):
         rc = lib.dcv_bias_grad(_p(Y), Y.stride(0), M, P, _p(dbias), _p(ws), ws.numel(), _stream())
     _check(rc, "dcv_bias_grad")
+
+
+def dino_loss_ws_floats(V, B, K) -> int:
+    return _ws_size(load().dcv_dino_loss_ws_floats(V, B, K))
+
+
+def dino_loss_plan(V, B, K, aligned=True) -> dict:
+    """The launch plan of dino_loss_fwd / dino_loss_bwd (include/dcv.h: dcv_dino_loss_plan) — host logic, callable without a GPU."""
+    vec, tile_cols, col_tiles, wpw, grid, passes = (C.c_int() for _ in range(6))
+    items = C.c_long()
+    rc = load().dcv_dino_loss_plan(V, B, K, int(bool(aligned)), C.addressof(vec), C.addressof(tile_cols), C.addressof(col_tiles),
+                                   C.addressof(items), C.addressof(wpw), C.addressof(grid), C.addressof(passes))
+    _check(rc, "dcv_dino_loss_plan")
+    return dict(vec=vec.value, tile_cols=tile_cols.value, col_tiles=col_tiles.value, items=items.value, waves_per_wg=wpw.value, grid=grid.value,
+                passes=passes.value)
+
+
+def _dino_operands(S, T, center, V):
+    for t, name in ((S, "S"), (T, "T")):
+        if not t.is_cuda:
+            raise RuntimeError(f"{name}: expected a GPU tensor (the HIP path has no CPU fallback)")
+        if t.dtype != torch.float32:
+            raise RuntimeError(f"{name}: expected {torch.float32}, got {t.dtype}")
+        if t.dim() != 2 or t.stride(1) != 1:
+            raise RuntimeError(f"{name}: expected a [rows, K] tensor with unit column stride")
+    _req(center, torch.float32, "center")
+    K = S.shape[1]
+    if V < 2 or S.shape[0] % V or T.shape[0] % 2 or S.shape[0] // V != T.shape[0] // 2 or T.shape[1] != K or center.numel() != K:
+        raise ValueError("dino_loss: S holds V*B rows of K logits (V >= 2), T 2*B rows of K, center K floats")
+    return S.shape[0] // V, K
+
+
+def dino_loss_fwd(S, T, center, V, student_temp, teacher_temp, loss, s_stats=None, t_stats=None, tsum=None, ws=None):
+    """loss[0] = DINO's multi-crop loss of the student logits S [V*B, K] (view-major, views 0 and 1 global) against the teacher logits T [2*B, K]
+    and the centre (include/dcv.h: dcv_dino_loss_fwd); rows S.stride(0) / T.stride(0) >= K apart.  s_stats [V*B, 2], t_stats [2*B, 3]: the row
+    statistics dino_loss_bwd reads; tsum [K]: the column sums of T; each written unless None.  Always deterministic: the kernels have no other
+    form.  ws: the caller's workspace of >= dino_loss_ws_floats(V, B, K) floats (tests); by default the stream's shared one."""
+    B, K = _dino_operands(S, T, center, V)
+    _req(loss, torch.float32, "loss")
+    for t, name, n in ((s_stats, "s_stats", 2 * V * B), (t_stats, "t_stats", 6 * B), (tsum, "tsum", K)):
+        if t is not None:
+            _req(t, torch.float32, name)
+            if t.numel() < n:
+                raise ValueError(f"dino_loss_fwd: {name} holds {n} floats")
+    lib = load()
+    if ws is None:
+        ws = _workspace(_ws_size(lib.dcv_dino_loss_ws_floats(V, B, K)), S)
+    else:
+        _req(ws, torch.float32, "ws")
+    with _timer(lambda: ("dino_loss_fwd_kernel", f"V{V} B{B} K{K}", 0.0, None, 4.0 * K * (B * (V + 2 + (2 if tsum is not None else 0)) + 1))):
+        rc = lib.dcv_dino_loss_fwd(_p(S), S.stride(0), _p(T), T.stride(0), _p(center), V, B, K, float(student_temp), float(teacher_temp), _p(loss),
+                                   _p(s_stats), _p(t_stats), _p(tsum), _p(ws), ws.numel(), _stream())
+    _check(rc, "dcv_dino_loss_fwd")
+
+
+def dino_loss_bwd(S, T, center, V, student_temp, teacher_temp, s_stats, t_stats, g, dS):
+    """dS [V*B, K] (rows dS.stride(0) >= K apart) = g[0] * d loss / d S from the statistics dino_loss_fwd saved (include/dcv.h: dcv_dino_loss_bwd);
+    g: the incoming gradient, one float on the device."""
+    B, K = _dino_operands(S, T, center, V)
+    _req(s_stats, torch.float32, "s_stats"); _req(t_stats, torch.float32, "t_stats"); _req(g, torch.float32, "g")
+    if not dS.is_cuda or dS.dtype != torch.float32 or dS.dim() != 2 or dS.stride(1) != 1 or dS.shape != S.shape:
+        raise RuntimeError("dS: expected a float32 GPU tensor of S's shape with unit column stride")
+    if s_stats.numel() < 2 * V * B or t_stats.numel() < 6 * B or g.numel() != 1:
+        raise ValueError("dino_loss_bwd: s_stats holds 2*V*B floats, t_stats 6*B, g one")
+    with _timer(lambda: ("dino_loss_bwd_kernel", f"V{V} B{B} K{K}", 0.0, None, 4.0 * K * (B * (2 * V + 2) + 1))):
+        rc = load().dcv_dino_loss_bwd(_p(S), S.stride(0), _p(T), T.stride(0), _p(center), _p(s_stats), _p(t_stats), _p(g), V, B, K,
+                                      float(student_temp), float(teacher_temp), _p(dS), dS.stride(0), _stream())
+    _check(rc, "dcv_dino_loss_bwd")
 
 
 def ln_fwd(x, gamma, beta, out, mean, rstd, M, D, eps, x_row_stride=None):

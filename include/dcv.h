@@ -340,6 +340,37 @@ int dcv_ortho_bwd(const float* Y, const float* S, const float* tot, const float*
 int dcv_proxy_loss_supported(int C, int D);
 int dcv_proxy_loss(const float* emb, const float* proxies, int C, int D, float scale, float* loss, float* d_emb, float* d_proxies, void* stream);
 
+/* DINO's multi-crop self-distillation loss (facebookresearch DINO, DINOLoss), value and gradient, fp32 in and out.  S: student logits [V, B, K],
+ * view-major, views 0 and 1 the global crops, rows lds floats apart; T: teacher logits [2, B, K] of the global crops, rows ldt apart; center [K].
+ * With q_i = softmax((T_i - center) / teacher_temp), p_v = softmax(S_v / student_temp), n = 2V - 2, m_v = 1 for v < 2 else 2, Q_v = sum_{i != v} q_i:
+ *   loss[0] = 1 / (n B) sum_v sum_b [ m_v lse(S_v[b] / student_temp) - <Q_v[b], S_v[b]> / student_temp ]        (dcv_dino_loss_fwd)
+ *   dS_v[b,k] = g[0] (m_v p_v[b,k] - Q_v[b,k]) / (n B student_temp), rows ldd apart, written once             (dcv_dino_loss_bwd)
+ * g is read on the device (the incoming gradient: no host synchronisation).  The forward is three launches: one pass over S, T and center that
+ * leaves per-(batch row, column tile) partial maxima, sums of exponentials and dots in ws, a finish that merges them in tile order and forms
+ * tsum, and a one-block sum of the B row terms (in double).  Besides loss it writes, each unless NULL: s_stats [V B, 2], per row (max, sum of exponentials relative to it) of S /
+ * student_temp, and t_stats [2 B, 3], per row (max, the max's low part, sum) of (T - center) / teacher_temp with T - center carried as fl(T - center) plus its
+ * exact rounding error — what the backward reads; the log-sum-exp is
+ * max / temp + ln(sum) — and tsum [K] = sum_{i,b} T_i[b,k], the centre statistics (formed in the finish launch from a second read of T).  The
+ * backward is one launch: S, T, center read once more, dS written once; no probability tensor ever reaches memory.  ALWAYS deterministic: no
+ * atomics, and every summation order is a function of (V, B, K) alone — not of the strides, the alignment or the grid.  16-byte loads and stores when
+ * every matrix pointer is 16-byte aligned and K and every stride are multiples of 4, 4-byte ones on the same columns otherwise; columns >= K of a
+ * row are never read (padding may hold anything).  ws: at least dcv_dino_loss_ws_floats(V, B, K) floats, contents irrelevant before and after.
+ * Checked before any HIP call: a required pointer NULL -> DCV_ERR_NULL; V < 2, B < 1, K < 1, a stride below K, a temperature that is not
+ * positive, ws_floats too small -> DCV_ERR_SHAPE; a row of 2 GB or more (with its last tile) -> DCV_ERR_UNSUPPORTED; a pointer off 4 bytes
+ * (ws: 16) -> DCV_ERR_ALIGN. */
+long dcv_dino_loss_ws_floats(int V, int B, int K);
+int dcv_dino_loss_fwd(const float* S, long lds, const float* T, long ldt, const float* center, int V, int B, int K, float student_temp,
+                      float teacher_temp, float* loss, float* s_stats, float* t_stats, float* tsum, float* ws, long ws_floats, void* stream);
+int dcv_dino_loss_bwd(const float* S, long lds, const float* T, long ldt, const float* center, const float* s_stats, const float* t_stats,
+                      const float* g, int V, int B, int K, float student_temp, float teacher_temp, float* dS, long ldd, void* stream);
+/* their launch plan — host logic, no GPU call.  aligned: does the call meet the 16-byte condition above.  A row's columns fall into col_tiles
+ * tiles of tile_cols = 1024; one wave owns one item = (batch row b, tile), item = b * col_tiles + tile, for every view, and lane l holds the 16
+ * columns tile * tile_cols + (64 u + l) * 4 + e, u, e < 4 (slot 4 u + e), loaded vec = 4 or 1 floats at a time.  A workgroup is waves_per_wg = 4
+ * waves; wave w of workgroup x takes in pass r the item (x + r * grid) * waves_per_wg + w (none past `items`); grid = min(ceil(items / 4), 2048),
+ * passes = 1 below the cap.  ws holds items * (6 + 4 V) + 2 B floats. */
+int dcv_dino_loss_plan(int V, int B, int K, int aligned, int* vec, int* tile_cols, int* col_tiles, long* items, int* waves_per_wg, int* grid,
+                       int* passes);
+
 /* fused AdamW over a flat fp32 range; g is multiplied by grad_scale first (1/world for data parallel). */
 int dcv_adamw(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2, float eps,
               float weight_decay, int step, float grad_scale, void* stream);
