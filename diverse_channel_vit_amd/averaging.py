@@ -39,7 +39,7 @@ class AveragedModel(nn.Module):
         self.avg, self.decay = avg, float(decay)
         # the copy owns its parameters (Parameter.__deepcopy__ clones them) and rebuilds its own arena and operand copies on first use; the
         # source's device buffers and its DataParallel reducer are left out of the copy instead of being duplicated and then dropped
-        skip = ("_dp", "_arena", "_grad_arena", "_grad_scratch", "_bf16", "_bf16_t", "_side")
+        skip = ("_dp", "_arena", "_grad_arena", "_grad_scratch", "_ops", "_side")
         memo = {id(v): None for v in (getattr(model, k, None) for k in skip) if v is not None}
         self.module = copy.deepcopy(model, memo)
         self.module._dp = None

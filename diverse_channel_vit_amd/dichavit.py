@@ -35,6 +35,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import hip
+from .operands import _OperandCopies
 
 LN_EPS = 1e-6  # models/dichavit.py:688,706,724,742
 _ATTN_SCALE = 64 ** -0.5  # head_dim ** -0.5: every size has 64-wide heads
@@ -457,11 +458,8 @@ class _EncoderFn(torch.autograd.Function):
                                 st_scale=model._cur_scale, st_shift=model._cur_shift, tok=tok, **({} if frozen_k is None else dict(frozen_k=frozen_k)),
                                 **({} if taps is None else dict(taps=taps)),
                                 **({} if all(plan.params) else dict(gplan=plan)))  # everything asked (or a reducer attached): the full backward, as ever
-        if need[6]:  # dcv_patch_dgrad's operands: the bf16 projection copy this forward multiplied by, the channel index, the input affine's scale
-            fe = model.feature_extractor
-            P = fe.patch_size
-            st.update(dx_req=True, Wp=model._bf(fe.patch_embed.proj.weight), ch_idx=ch_idx_dev, in_scale=model._cur_scale, Ct=x.shape[1],
-                      Hi=x.shape[2], Wi=x.shape[3], P=P)
+        if need[6]:  # dcv_patch_dgrad's operands besides the projection copy of st["ops"]: the channel index, the input affine's scale
+            st.update(dx_req=True, ch_idx=ch_idx_dev, in_scale=model._cur_scale, Ct=x.shape[1], Hi=x.shape[2], Wi=x.shape[3], P=model.feature_extractor.patch_size)
             if plan.data_only:  # the plan with every entry "no / no" and nothing asked: the gradient arena is not touched
                 st["data_only"] = True
         ctx.model = model
@@ -699,7 +697,7 @@ class DiChaViT(nn.Module):
         self.adaptive_interface = nn.ParameterList([self.proxies])  # :812 (state_dict alias key)
         self.feature_extractor._owner = weakref.ref(self)  # get_last_selfattention (re-linked by __setstate__: deepcopy / unpickle)
         # --- HIP-path state (not part of the state_dict) ---
-        self._arena = None
+        self._arena = self._ops = None  # the fp32 parameter arena and the model's own set of bf16 operand copies of it (operands._OperandCopies)
         self._grad_arena = None
         self._grad_scratch = None
         self._dp = None  # set by diverse_channel_vit_amd.dp.DataParallel
@@ -783,57 +781,22 @@ class DiChaViT(nn.Module):
         self._enc_size = offs[len(enc)] if others else off
         self._grad_arena = None
         self._grad_scratch = None
-        self._bf16 = torch.empty(self._enc_size, dtype=torch.bfloat16, device=device)    # same offsets as the arena
-        self._bf16_t = torch.empty(self._enc_size, dtype=torch.bfloat16, device=device)  # transposed copies of matrices
-        # transposed copies are needed for the four Linear weights of every block (input-gradient GEMMs)
-        desc, max_tiles = [], 1
-        self._w_index = {}
-        for i, p in enumerate(enc):
-            self._w_index[id(p)] = i
-        for b in self.feature_extractor.blocks:
-            for w in (b.attn.qkv.weight, b.attn.proj.weight, b.mlp.fc1.weight, b.mlp.fc2.weight):
-                o = self._enc_off[self._w_index[id(w)]]
-                R, Cc = w.shape
-                desc.append([o, o, R, Cc])
-                max_tiles = max(max_tiles, ((R + 63) // 64) * ((Cc + 63) // 64))
-        self._tdesc = torch.tensor(desc, dtype=torch.int64, device=device)
-        self._tdesc_n, self._tdesc_tiles = len(desc), max_tiles
-        # pre-scaled q: per block, the q rows of the qkv weight copy (kind 0, in place in the bf16 copy) and the qkv bias with its q part scaled (kind 1)
-        qdesc, Dm = [], self.dim
-        for li, b in enumerate(self.feature_extractor.blocks):
-            ow, ob = self._enc_off[self._w_index[id(b.attn.qkv.weight)]], self._enc_off[self._w_index[id(b.attn.qkv.bias)]]
-            qdesc.append([ow, ow, Dm * Dm, Dm * Dm, 0])
-            qdesc.append([ob, li * 3 * Dm, 3 * Dm, Dm, 1])
-        self._qdesc = torch.tensor(qdesc, dtype=torch.int64, device=device)
-        self._qbias = torch.empty(len(self.feature_extractor.blocks), 3 * Dm, dtype=torch.float32, device=device)
+        self._slot_of = {id(p): o for p, o in zip(enc, self._enc_off)}
+        self._ops = _OperandCopies.for_encoder(self._slot_of, self._enc_size, self.feature_extractor.blocks, self.dim, _Q_PRESCALE, device)
 
-    def _bf(self, p, transposed=False, buf=None):
-        """buf: a straight copy other than self._bf16 (the scratch copy of get_last_selfattention)."""
-        o = self._enc_off[self._w_index[id(p)]]
-        if buf is None:
-            buf = self._bf16_t if transposed else self._bf16
-        v = buf[o:o + p.numel()]
-        if p.dim() >= 2:
-            R = p.shape[0]
-            return v.view(p.numel() // R, R) if transposed else v.view(R, p.numel() // R)
-        return v
+    def _slot(self, p):
+        """Where encoder parameter p starts in the arena, the gradient arena and the operand copies, in elements."""
+        return self._slot_of[id(p)]
 
-    def _refresh_operand_copies(self, stochastic: bool = False, prescale_q: bool = False):
-        """prescale_q: W_q rows of the straight copy and the q part of the bias copy times scale * log2(e) (attn_prescaled); the transposed copy
-        stays unscaled (the input-gradient GEMM multiplies by it the gradient with respect to the unscaled q)."""
-        if stochastic:
-            if self._sr_seed is None or self._sr_seed.device != self._arena.device:
-                self._sr_seed = torch.full((1,), int(_cfg_get(self.cfg, "weight_rounding_seed", 1)), dtype=torch.int32, device=self._arena.device)
-            hip.cast_bf16_sr(self._arena, self._bf16, self._enc_size, self._sr_seed)
-            hip.cast_transpose_bf16_sr(self._arena, self._bf16_t, self._tdesc, self._tdesc_n, self._tdesc_tiles, self._sr_seed)
-            if prescale_q:
-                hip.cast_scaled_ranges(self._arena, self._bf16, self._qbias, self._qdesc, self._qdesc.shape[0], 64, _Q_PRESCALE, self._sr_seed)
+    def _refresh_own_copies(self, save):
+        """The model's own set from the arena: stochastically rounded for a training forward that saves for a backward (one draw, then the
+        seed's bump), round-to-nearest otherwise.  Private sets (inspection calls) never draw."""
+        sr = bool(save) and self.training and self.stochastic_weight_rounding
+        if sr and (self._sr_seed is None or self._sr_seed.device != self._arena.device):
+            self._sr_seed = torch.full((1,), int(_cfg_get(self.cfg, "weight_rounding_seed", 1)), dtype=torch.int32, device=self._arena.device)
+        self._ops.refresh(self._arena, prescale_q=bool(self.attn_prescaled), seed=self._sr_seed if sr else None)
+        if sr:
             self._sr_seed.add_(1)  # a device-side bump: replays of a captured step draw fresh bits too
-            return
-        hip.cast_bf16(self._arena, self._bf16, self._enc_size)
-        hip.cast_transpose_bf16(self._arena, self._bf16_t, self._tdesc, self._tdesc_n, self._tdesc_tiles)
-        if prescale_q:
-            hip.cast_scaled_ranges(self._arena, self._bf16, self._qbias, self._qdesc, self._qdesc.shape[0], 64, _Q_PRESCALE)
 
     def _new_grad_arena(self):
         """A zeroed flat gradient buffer for the encoder parameters.  The arena is reused when no parameter's .grad still aliases it
@@ -1143,18 +1106,17 @@ class DiChaViT(nn.Module):
             out.append(tuple(pair))
         return out
 
-    def _tokenise(self, x, ch_idx_dev, C, E, pos_tab, want_ortho, keep, st_scale, st_shift, tok, wbuf=None, qbias=None):
+    def _tokenise(self, x, ch_idx_dev, C, E, pos_tab, want_ortho, keep, st_scale, st_shift, tok, ops):
         """The tokeniser: im2col -> MFMA GEMM with (+bias +channel_embed[c] +pos[i]) epilogue, CLS fill, ortho statistics, token gather.
-        wbuf / qbias: straight bf16 operand copies and q bias other than the model's own (_inspection_tokenise).  Returns (f, the residual
-        stream [M, D], the ortho statistics [B, 2], what the tokeniser's backward needs); f is what the blocks of this forward share: the
-        shapes the encoder sees, `wb(p)` (the bf16 operand copy of p), the q bias, pre-scaled q or not, DropPath factors, fused LayerNorm or not."""
+        ops: the set of bf16 operand copies this forward multiplies by (_OperandCopies).  Returns (f, the residual stream [M, D], the ortho
+        statistics [B, 2], what the tokeniser's backward needs); f is what the blocks of this forward share: the shapes the encoder sees, `ops`,
+        pre-scaled q or not (a property of the set), DropPath factors, fused LayerNorm or not."""
         fe, dev = self.feature_extractor, x.device
         pe, D, P = fe.patch_embed, self.dim, fe.patch_size
         B, Ct, Hi, Wi = x.shape
         n = (Hi // P) * (Wi // P)
         T, N = C * n, C * n + 1
         bf, f32 = torch.bfloat16, torch.float32
-        wb = lambda p: self._bf(p, buf=wbuf)  # noqa: E731
         # (channels, positions) structure of the embedding rows the tokeniser epilogue adds: (C, n) normally, (1, C*n) when the
         # positional table is per token (the reference's early-out, _pos_table)
         Ctok, ntok = tok if tok is not None else (C, n)
@@ -1163,7 +1125,7 @@ class DiChaViT(nn.Module):
         xs = torch.empty(B, N, D, dtype=f32, device=dev)
         Y = torch.empty(B * T, D, dtype=f32, device=dev) if want_ortho else None
         Ec, pc = E.contiguous(), pos_tab.contiguous()
-        hip.gemm_nt(Xp, wb(pe.proj.weight), hip.EPI_PATCH, xs, bias=pe.proj.bias, out2=Y, aux=Ec, aux2=pc, T=T, n=ntok,
+        hip.gemm_nt(Xp, ops.w(pe.proj.weight), hip.EPI_PATCH, xs, bias=pe.proj.bias, out2=Y, aux=Ec, aux2=pc, T=T, n=ntok,
                     ldo=D, ldo2=D, ldaux=D)
         hip.fill_cls(xs, fe.cls_token, pc, B, N * D, D)
         stats = torch.zeros(B, 2, dtype=f32, device=dev)
@@ -1184,8 +1146,8 @@ class DiChaViT(nn.Module):
         # on the narrow kernel's three-times-as-many tiles plus a separate ln_fwd is faster (measured: CHAMMI step 29.5 vs 30.6 ms, bs 16 equal, bs 32
         # 19.1 -> 18.6 ms, bs 64 36.45 -> 35.85 ms)
         fuse_ln = bool(self.fuse_ln_fwd) and D == 384 and (M + 255) // 256 >= self.fuse_ln_min_tiles
-        f = types.SimpleNamespace(B=B, C=C, n=n, N=N, M=M, D=D, H=fe.num_heads, dev=dev, tok=(Ctok, ntok), wb=wb, ps=bool(self.attn_prescaled),
-                                  qbias=self._qbias if qbias is None else qbias, drop=self._drop_path_scales(B, dev), fuse_ln=fuse_ln)
+        f = types.SimpleNamespace(B=B, C=C, n=n, N=N, M=M, D=D, H=fe.num_heads, dev=dev, tok=(Ctok, ntok), ops=ops, ps=ops.prescaled,
+                                  drop=self._drop_path_scales(B, dev), fuse_ln=fuse_ln)
         return f, xs.view(M, D), stats, kept
 
     def _block_attention(self, f, bi, xcur, pre_ln, nq=None):
@@ -1202,7 +1164,7 @@ class DiChaViT(nn.Module):
             mean1, rstd1 = torch.empty(M, dtype=f32, device=dev), torch.empty(M, dtype=f32, device=dev)
             hip.ln_fwd(xcur, blk.norm1.weight, blk.norm1.bias, u1, mean1, rstd1, M, D, LN_EPS)
         qkv = torch.empty(M, 3 * D, dtype=bf, device=dev)
-        hip.gemm_nt(u1, f.wb(blk.attn.qkv.weight), hip.EPI_BIAS_BF16, qkv, bias=f.qbias[bi] if f.ps else blk.attn.qkv.bias)
+        hip.gemm_nt(u1, f.ops.w(blk.attn.qkv.weight), hip.EPI_BIAS_BF16, qkv, bias=f.ops.qbias[bi] if f.ps else blk.attn.qkv.bias)
         o = torch.empty(M, D, dtype=bf, device=dev)
         lse = torch.empty(B, H, N, dtype=f32, device=dev)
         hip.attn_fwd(qkv, o, lse, B, N, H, D // H, _ATTN_SCALE, prescaled=f.ps, **({} if nq is None else dict(nq=nq)))
@@ -1217,7 +1179,7 @@ class DiChaViT(nn.Module):
         blk, nxt = fe.blocks[bi], fe.blocks[bi + 1] if bi + 1 < len(fe.blocks) else None
         B, N, M, D, dev = f.B, f.N, f.M, f.D, f.dev
         bf, f32 = torch.bfloat16, torch.float32
-        o, wb = a["o"], f.wb
+        o, wb = a["o"], f.ops.w
         dsc = f.drop[bi] if f.drop is not None else None  # (attention branch, MLP branch) DropPath factors [B] or None
         if tail:
             # The encoder's output is read at the CLS row only (norm(x)[:, 0], dichavit.py:651-652), so in the LAST block
@@ -1311,12 +1273,12 @@ class DiChaViT(nn.Module):
             hip.ln_bwd(dtap.view(B * N, D), x, stats[0], stats[1], fe.norm.weight, dx, dx, None, gw, gb, B * N, D)
 
     def _run_forward(self, x, ch_idx_dev, C, E, pos_tab, want_ortho, save, keep=None, st_scale=None, st_shift=None, tok=None, frozen_k=None,
-                     refresh=True, taps=None, gplan=None):
+                     ops=None, taps=None, gplan=None):
         """The training / eval forward: operand copies, tokeniser, blocks, final norm.  Returns the state: feat, stats and, with save, what the
         backward reads.  frozen_k=k (with save): blocks < k and the tokeniser keep nothing for the backward (they run as with save=False, on
         the same kernels); st["layers"] still has one entry per block — the backward indexes it by block number — which for blocks < k holds
-        the DropPath factors only.  refresh=False: the operand copies are the caller's business (_probe_relevance); inside forward_views they
-        are its business too (_copies_held).
+        the DropPath factors only.  ops: the set of operand copies to multiply by, used as it stands (_probe_relevance); None: the model's own,
+        refreshed here unless forward_views has done so (_copies_held).  With save, st["ops"] names the set: the backward multiplies by it.
         gplan (with save): the gradient plan (_grad_plan), kept as st["gplan"]: the X operand of a weight gradient nobody asked for — h, u2, u1 of
         a block, the tokeniser's Xp — is not kept (the launches are the same).  None: everything is kept.
         taps=(blocks, pool) (forward_with_features): st["tap_out"] lists the final norm of the stream after each listed block, launched right
@@ -1324,12 +1286,13 @@ class DiChaViT(nn.Module):
         what their backward reads: the streams themselves — block l + 1's saved x_in, x_final for the last block: no copy — and the row
         statistics of the pools that go through dcv_ln_bwd."""
         depth = len(self.feature_extractor.blocks)
-        if refresh and not self._copies_held:
-            self._refresh_operand_copies(stochastic=bool(save) and self.training and self.stochastic_weight_rounding, prescale_q=bool(self.attn_prescaled))
-        f, xcur, stats, kept = self._tokenise(x, ch_idx_dev, C, E, pos_tab, want_ortho, keep, st_scale, st_shift, tok)
+        if ops is None and not self._copies_held:
+            self._refresh_own_copies(save)
+        ops = self._ops if ops is None else ops
+        f, xcur, stats, kept = self._tokenise(x, ch_idx_dev, C, E, pos_tab, want_ortho, keep, st_scale, st_shift, tok, ops)
         fk = frozen_k if save else None
         gplan = gplan if save else None
-        st = dict(B=f.B, C=C, n=f.n, N=f.N, M=f.M, save=save, tok=f.tok, ps=f.ps, frozen_k=fk, gplan=gplan)
+        st = dict(B=f.B, C=C, n=f.n, N=f.N, M=f.M, save=save, tok=f.tok, frozen_k=fk, gplan=gplan)
         if save and self._copies_held > 1:
             st["private_grads"] = True  # one of several nodes that meet in ONE backward (forward_views): _asked_grads
         if save and fk is None:
@@ -1357,13 +1320,13 @@ class DiChaViT(nn.Module):
         if taps is not None:
             st.update(tap_out=tap_out, tap_blocks=tuple(tap_blocks))
         if save:
-            st.update(layers=layers, x_final=xcur, final_stride=final_stride, meanf=meanf, rstdf=rstdf, want_ortho=want_ortho)
+            st.update(ops=ops, layers=layers, x_final=xcur, final_stride=final_stride, meanf=meanf, rstdf=rstdf, want_ortho=want_ortho)
             if taps is not None:
                 st["taps"] = tp
         return st
 
     def _gview(self, ga, p):
-        o = self._enc_off[self._w_index[id(p)]]
+        o = self._slot(p)
         return ga[o:o + p.numel()].view(p.shape)
 
     def _run_backward(self, st, dfeat, dstats):
@@ -1444,8 +1407,8 @@ class DiChaViT(nn.Module):
         Ms = M if k0 < len(fe.blocks) else 0  # fk == depth: only the final LayerNorm's backward (above) runs
         sc = _BackwardScratch(self._side_stream(dev) if self.wgrad_stream else None, dev, ga is not None, bool(self.wgrad_private_scratch),
                               dxb=dxb, dz=torch.empty(Ms, 4 * D, dtype=bf, device=dev), dqkv=torch.empty(Ms, 3 * D, dtype=bf, device=dev))
-        # what the blocks' backwards share; ps: the forward of this pass ran with pre-scaled q: qkv holds q', the backward entries must match
-        b = types.SimpleNamespace(B=B, N=N, M=M, g=g, nt_kw=nt_kw, ps=bool(st.get("ps")), sc=sc,
+        # what the blocks' backwards share; ops: the forward's set of operand copies; ps: it ran with pre-scaled q: qkv holds q', the backward entries must match
+        b = types.SimpleNamespace(B=B, N=N, M=M, g=g, nt_kw=nt_kw, ops=st["ops"], ps=st["ops"].prescaled, sc=sc,
                                   du=torch.empty(Ms, D, dtype=bf, device=dev), dO=torch.empty(Ms, D, dtype=bf, device=dev),
                                   delta=torch.empty(2, B, H, N if Ms else 0, dtype=f32, device=dev),  # attention backward workspace: -delta, lse*log2e
                                   probe=st.get("probe"),  # get_attention_relevance: called with (L, b) once a block's b.dO is written
@@ -1492,9 +1455,9 @@ class DiChaViT(nn.Module):
         # MLP
         dxb, dz = sc.dxb, sc.fresh("dz")
         dz_ = dz[:R] if tail else dz
-        hip.gemm_nt(dxb, self._bf(blk.mlp.fc2.weight, True), hip.EPI_GELU_BWD_BF16, dz_, aux=L["z"], **nt_kw)
+        hip.gemm_nt(dxb, b.ops.wt(blk.mlp.fc2.weight), hip.EPI_GELU_BWD_BF16, dz_, aux=L["z"], **nt_kw)
         sc.wgrad(dxb, L.get("h"), g(blk.mlp.fc2.weight), g(blk.mlp.fc2.bias))
-        hip.gemm_nt(dz_, self._bf(blk.mlp.fc1.weight, True), hip.EPI_PLAIN_BF16, du_, **nt_kw)
+        hip.gemm_nt(dz_, b.ops.wt(blk.mlp.fc1.weight), hip.EPI_PLAIN_BF16, du_, **nt_kw)
         sc.wgrad(dz_, L.get("u2"), g(blk.mlp.fc1.weight), g(blk.mlp.fc1.bias))
         dxb = sc.fresh("dxb")
         dsc = L.get("drop")  # this block's (attention, MLP) DropPath factors: the copy written here feeds its attention branch
@@ -1503,7 +1466,7 @@ class DiChaViT(nn.Module):
         # attention
         if tail:
             dO_c = b.du[B:2 * B]  # scratch rows of the same buffer
-            hip.gemm_nt(dxb, self._bf(blk.attn.proj.weight, True), hip.EPI_PLAIN_BF16, dO_c, **nt_kw)
+            hip.gemm_nt(dxb, b.ops.wt(blk.attn.proj.weight), hip.EPI_PLAIN_BF16, dO_c, **nt_kw)
             sc.wgrad(dxb, L["o_c"], g(blk.attn.proj.weight), g(blk.attn.proj.bias))  # the tail has no side stream and no group: launched here
             b.dO.view(B, N, D)[:, 0].copy_(dO_c)  # only the CLS rows of dO are read (nq = 1)
             if b.probe is not None:
@@ -1513,12 +1476,12 @@ class DiChaViT(nn.Module):
             dx.view(B, N, D)[:, 0].copy_(dx_c)
             sc.dxb = torch.empty(M, D, dtype=torch.bfloat16, device=dx.device)
         else:
-            hip.gemm_nt(dxb, self._bf(blk.attn.proj.weight, True), hip.EPI_PLAIN_BF16, b.dO, **nt_kw)
+            hip.gemm_nt(dxb, b.ops.wt(blk.attn.proj.weight), hip.EPI_PLAIN_BF16, b.dO, **nt_kw)
             if b.probe is not None:
                 b.probe(L, b)
             sc.wgrad(dxb, L["o"], g(blk.attn.proj.weight), g(blk.attn.proj.bias))
             hip.attn_bwd(L["qkv"], L["o"], b.dO, L["lse"], b.delta, sc.fresh("dqkv"), B, N, H, D // H, _ATTN_SCALE, prescaled=b.ps)
-        hip.gemm_nt(sc.dqkv, self._bf(blk.attn.qkv.weight, True), hip.EPI_PLAIN_BF16, b.du, **nt_kw)
+        hip.gemm_nt(sc.dqkv, b.ops.wt(blk.attn.qkv.weight), hip.EPI_PLAIN_BF16, b.du, **nt_kw)
         sc.wgrad(sc.dqkv, L.get("u1"), g(blk.attn.qkv.weight), g(blk.attn.qkv.bias))
         sc.launch_group()
         if li - 1 in b.dtaps:
@@ -1560,7 +1523,7 @@ class DiChaViT(nn.Module):
             # input images: dYb (the token gradients with the ortho term) through the projection's adjoint; the real (C, n), also when the
             # positional table is per token (tok = (1, C*n)): dYb's rows are (b, c, i, j) either way
             dxin = torch.empty(B, st["Ct"], st["Hi"], st["Wi"], dtype=f32, device=dev)
-            hip.patch_dgrad(dYb, st["Wp"], st["ch_idx"], dxin, B, st["Ct"], C, st["Hi"], st["Wi"], st["P"], scale=st["in_scale"])
+            hip.patch_dgrad(dYb, st["ops"].w(pe.proj.weight), st["ch_idx"], dxin, B, st["Ct"], C, st["Hi"], st["Wi"], st["P"], scale=st["in_scale"])
             st["dx_out"] = dxin
         if wgrads:  # the patch projection follows the plan's table like a block's layers
             gw, gb = g(pe.proj.weight), g(pe.proj.bias)
@@ -1622,10 +1585,7 @@ class DiChaViT(nn.Module):
 
     def _range_of(self, ps):
         """[start, end) of the arena slots between the first and the last parameter given (inclusive)."""
-        a = self._enc_off[self._w_index[id(ps[0])]]
-        last = ps[-1]
-        b = self._enc_off[self._w_index[id(last)]] + last.numel()
-        return a, b
+        return self._slot(ps[0]), self._slot(ps[-1]) + ps[-1].numel()
 
     # ---------------------------------------------------------------------------------------
     def forward(self, x: torch.Tensor, chunk_name: str, training_chunks: Optional[str] = None, init_first_layer=None,
@@ -1670,9 +1630,9 @@ class DiChaViT(nn.Module):
         resolution — except that the operand copies are refreshed once, before the first: one rounding draw and one _sr_seed bump per call with
         stochastic rounding on.  Returns (feats, extra): the CLS features after the final norm, concatenated in view order [sum of the batches, D],
         fp32 and connected to the graph, and the sum of the views' regularisers (a zero scalar in eval mode).
-        Why it exists: an encoder node's backward multiplies by the LIVE operand copies.  Two plain forwards before one backward leave the first
-        node with the second's copies — other weight bits under stochastic rounding.  Here every node of the call finds the copies its forward
-        used, as long as the backward runs before the next training forward of this model.  Backward order is autograd's.  With more than one view
+        Why it exists: a node's backward multiplies by the set its forward's state names (st["ops"]).  Two plain training forwards before one backward
+        still share the model's one set: the first backward therefore reads the second forward's bits.  forward_views is the supported way: every node
+        finds the copies its forward used, as long as the backward runs before the next training forward of this model.  Backward order is autograd's.  With more than one view
         every node hands autograd a private copy of its parameter gradients (they meet in one backward, where the shared gradient arena cannot
         be told free from in use); .grad is their sum and does not live in the arena, so HipAdamW takes its per-parameter path for that step.  The classifier head's output is not returned (its parameters receive no
         gradient from this call: freeze them or leave them out of the optimiser).
@@ -1698,7 +1658,7 @@ class DiChaViT(nn.Module):
                                             (hasattr(pe, "channel_embed") and pe.channel_embed.weight.requires_grad) or
                                             any(p.requires_grad for p in self._enc_param_list()))
         with torch.autocast(device_type="cuda", enabled=False):
-            self._refresh_operand_copies(stochastic=save and self.training and self.stochastic_weight_rounding, prescale_q=bool(self.attn_prescaled))
+            self._refresh_own_copies(save)
         self._copies_held = len(views)
         try:
             feats, extra = [], None
@@ -1844,15 +1804,11 @@ class DiChaViT(nn.Module):
             yield self._prepare_tokens(x, chunk_name, training_chunks, new_channel_init)
 
     def _inspection_tokenise(self, tk):
-        """The tokeniser on scratch operand copies: the model's own (_bf16, _bf16_t, _qbias) and _sr_seed are left alone — a training
-        forward's backward may still read them — and round-to-nearest straight copies are cast into private buffers instead.  Returns
-        (f, the residual stream) as _tokenise does."""
-        wbuf, qbias = torch.empty_like(self._bf16), torch.empty_like(self._qbias)
-        hip.cast_bf16(self._arena, wbuf, self._enc_size)
-        if self.attn_prescaled:
-            hip.cast_scaled_ranges(self._arena, wbuf, qbias, self._qdesc, self._qdesc.shape[0], 64, _Q_PRESCALE)
-        f, xcur, _, _ = self._tokenise(tk.x, tk.ch_idx_dev, tk.C, tk.E_tok, tk.pos_tab, False, tk.keep, tk.scale, tk.shift, tk.tok, wbuf, qbias)
-        return f, xcur
+        """The tokeniser on a private, forward-only set of operand copies, round-to-nearest: the model's own set and _sr_seed are left alone — a
+        training forward's backward may still read them.  Returns (f, the residual stream) as _tokenise does; f.ops keeps the set alive."""
+        ops = self._ops.private(transposed=False)
+        ops.refresh(self._arena, prescale_q=bool(self.attn_prescaled))
+        return self._tokenise(tk.x, tk.ch_idx_dev, tk.C, tk.E_tok, tk.pos_tab, False, tk.keep, tk.scale, tk.shift, tk.tok, ops)[:2]
 
     @staticmethod
     def _token_count(tk):
@@ -1995,8 +1951,8 @@ class DiChaViT(nn.Module):
             return self._probe_relevance(x, chunk, training_chunks, new_channel_init, first, start, target)
 
     def _probe_relevance(self, x, chunk_name, training_chunks, new_channel_init, start_layer, start, target):
-        """get_attention_relevance: the forward of _EncoderFn with the blocks from start_layer up kept, on private round-to-nearest operand copies
-        (straight, transposed and the pre-scaled q bias, swapped in for the duration of the call), then the data-only backward down to block
+        """get_attention_relevance: the forward of _EncoderFn with the blocks from start_layer up kept, on a private round-to-nearest set of operand
+        copies (straight, transposed and the pre-scaled q bias) that its state carries to its backward, then the data-only backward down to block
         start_layer with a hook that launches dcv_attn_relevance_step on each block's qkv, LSE and dO between two ping-pong [B, N] buffers."""
         with self._inspection_tokens(x, chunk_name, training_chunks, new_channel_init) as tk:
             dev, D = tk.x.device, self.dim
@@ -2026,20 +1982,16 @@ class DiChaViT(nn.Module):
                 hip.attn_relevance_step(L["qkv"], L["lse"], b.dO, r, nxt, B, N, H, D // H, _ATTN_SCALE, nq=1 if L["tail"] else None, prescaled=b.ps)
                 r, nxt = nxt, r
 
-            own = self._bf16, self._bf16_t, self._qbias
-            self._bf16, self._bf16_t, self._qbias = (torch.empty_like(t) for t in own)
-            try:
-                self._refresh_operand_copies(stochastic=False, prescale_q=bool(self.attn_prescaled))
-                st = self._run_forward(tk.x, tk.ch_idx_dev, tk.C, tk.E_tok, tk.pos_tab, False, save=True, keep=tk.keep, st_scale=tk.scale,
-                                       st_shift=tk.shift, tok=tk.tok, frozen_k=start_layer, refresh=False)
-                if target is None:
-                    classes = head(st["feat"]).argmax(1)
-                dfeat = target if classes is None else head.weight.detach().float()[classes]
-                st.update(data_only=True, probe=step)
-                self._run_backward(st, dfeat.contiguous(), None)
-                st.clear()
-            finally:
-                self._bf16, self._bf16_t, self._qbias = own
+            ops = self._ops.private(transposed=True)
+            ops.refresh(self._arena, prescale_q=bool(self.attn_prescaled))
+            st = self._run_forward(tk.x, tk.ch_idx_dev, tk.C, tk.E_tok, tk.pos_tab, False, save=True, keep=tk.keep, st_scale=tk.scale,
+                                   st_shift=tk.shift, tok=tk.tok, frozen_k=start_layer, ops=ops)
+            if target is None:
+                classes = head(st["feat"]).argmax(1)
+            dfeat = target if classes is None else head.weight.detach().float()[classes]
+            st.update(data_only=True, probe=step)
+            self._run_backward(st, dfeat.contiguous(), None)
+            st.clear()
             return r
 
     def _ortho_from_stats(self, stats, C, n):
