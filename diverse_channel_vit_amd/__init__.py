@@ -13,8 +13,8 @@ from .graph import GraphedTrainStep  # noqa: F401
 from .averaging import AveragedModel  # noqa: F401
 from .augment import DeviceAugment, AugmentParams, tps_coefficients  # noqa: F401
 from .hip import set_deterministic, is_deterministic  # noqa: F401
-from .ssl import DINOLoss, DINOHead, teacher_temp_schedule, update_teacher_head  # noqa: F401
+from .ssl import DINOLoss, DINOHead, IBOTPatchLoss, BlockMaskGenerator, teacher_temp_schedule, update_teacher_head  # noqa: F401
 
 __all__ = ["DiChaViT", "dichavit", "proxy_loss", "DataParallel", "HipAdamW", "GraphedTrainStep", "AveragedModel", "DeviceAugment", "AugmentParams", "tps_coefficients", "clip_grad_norm_", "param_groups", "save_checkpoint", "load_checkpoint",
-           "evaluate", "dump_features", "eval_subset_channels", "set_deterministic", "is_deterministic", "DINOLoss", "DINOHead",
+           "evaluate", "dump_features", "eval_subset_channels", "set_deterministic", "is_deterministic", "DINOLoss", "DINOHead", "IBOTPatchLoss", "BlockMaskGenerator",
            "teacher_temp_schedule", "update_teacher_head"]

@@ -448,15 +448,18 @@ class _EncoderFn(torch.autograd.Function):
         return _EncoderFn._backward(ctx, dfeat, dstats)
 
     @staticmethod
-    def _forward(ctx, need, taps, model, ch_idx_dev, C, want_ortho, keep, tok, x, E, pos_tab):
-        """need: needs_input_grad as _EncoderFn.forward's arguments are numbered.  taps: None, or (blocks, pool) of _EncoderTapsFn."""
+    def _forward(ctx, need, taps, model, ch_idx_dev, C, want_ortho, keep, tok, x, E, pos_tab, mask=None):
+        """need: needs_input_grad as _EncoderFn.forward's arguments are numbered.  taps: None, or (blocks, pool) of _EncoderTapsFn.  mask: None, or
+        (masks, mask_token, does the mask token need a gradient) of _EncoderMaskFn."""
         # frozen prefix: nothing upstream of the first block k with a trainable parameter needs a gradient — not x, E, the positional table,
-        # cls_token or the patch projection (need[6:12]), and by k's definition no parameter of a block below it (12 per block from need[12])
-        plan = _grad_plan(need, len(model.feature_extractor.blocks), model._dp)
+        # cls_token or the patch projection (need[6:12]), and by k's definition no parameter of a block below it (12 per block from need[12]);
+        # a mask token that needs a gradient sits upstream of the blocks too
+        need_mt = mask is not None and bool(mask[2])
+        plan = _grad_plan(need, len(model.feature_extractor.blocks), model._dp, upstream=need_mt)
         frozen_k = plan.frozen_k
-        st = model._run_forward(x, ch_idx_dev, C, E, pos_tab, want_ortho, save=any(need), keep=keep,
+        st = model._run_forward(x, ch_idx_dev, C, E, pos_tab, want_ortho, save=any(need) or need_mt, keep=keep,
                                 st_scale=model._cur_scale, st_shift=model._cur_shift, tok=tok, **({} if frozen_k is None else dict(frozen_k=frozen_k)),
-                                **({} if taps is None else dict(taps=taps)),
+                                **({} if taps is None else dict(taps=taps)), **({} if mask is None else dict(mask=mask)),
                                 **({} if all(plan.params) else dict(gplan=plan)))  # everything asked (or a reducer attached): the full backward, as ever
         if need[6]:  # dcv_patch_dgrad's operands besides the projection copy of st["ops"]: the channel index, the input affine's scale
             st.update(dx_req=True, ch_idx=ch_idx_dev, in_scale=model._cur_scale, Ct=x.shape[1], Hi=x.shape[2], Wi=x.shape[3], P=model.feature_extractor.patch_size)
@@ -502,6 +505,32 @@ class _EncoderTapsFn(_EncoderFn):
         return (None,) + _EncoderFn._backward(ctx, dfeat, dstats)
 
 
+class _EncoderMaskFn(_EncoderFn):
+    """_EncoderFn with masked patch tokens (masks= of forward / forward_with_features): `masks` (uint8 [B, C n]) and `mask_token` come first, then
+    `taps` ((blocks, pool) or None), then _EncoderFn's arguments, whose numbering _grad_plan keeps; the taps follow feat and stats as in
+    _EncoderTapsFn.  The masked rows of the token stream are rewritten after the tokeniser's GEMM (dcv_mask_tokens_fwd); the backward returns
+    dmask_token in front (dcv_mask_tokens_bwd, inside the tokeniser's backward)."""
+
+    @staticmethod
+    def forward(ctx, masks, mask_token, taps, model, ch_idx_dev, C, want_ortho, keep, tok, x, E, pos_tab, *params):
+        feat, stats = _EncoderFn._forward(ctx, ctx.needs_input_grad[3:], taps, model, ch_idx_dev, C, want_ortho, keep, tok, x, E, pos_tab,
+                                          mask=(masks, mask_token, ctx.needs_input_grad[1]))
+        ctx.set_materialize_grads(False)
+        return (feat, stats) + tuple(ctx.st.pop("tap_out", ()))
+
+    @staticmethod
+    def backward(ctx, dfeat, dstats, *dtaps):
+        st = ctx.st
+        if dfeat is None:
+            dfeat = torch.zeros_like(st["feat"])
+        if "tap_blocks" in st:
+            st["dtaps"] = {l: d for l, d in zip(st["tap_blocks"], dtaps) if d is not None}
+        out = {}
+        st["mask_out"] = out  # _backward clears st: the tokeniser's backward leaves dmask_token here
+        grads = _EncoderFn._backward(ctx, dfeat, dstats)
+        return (None, out.get("dmask_token"), None) + grads
+
+
 def _frozen_prefix(upstream: bool, blocks, norm: bool, dp) -> Optional[int]:
     """The frozen prefix of a forward: the first block with a trainable parameter (len(blocks) when only the final norm has one) when nothing
     upstream of the blocks needs a gradient and no DataParallel reducer is attached; None when there is no prefix.  blocks: per block, does
@@ -514,7 +543,7 @@ def _frozen_prefix(upstream: bool, blocks, norm: bool, dp) -> Optional[int]:
 _LINEARS = (("qkv", 2), ("proj", 4), ("fc1", 8), ("fc2", 10))  # a block's linear layers: name, place of the weight among the block's 12 parameters (the bias follows)
 
 
-def _grad_plan(need, depth: int, dp):
+def _grad_plan(need, depth: int, dp, upstream: bool = False):
     """The gradient plan of a forward, from `need`: needs_input_grad as _EncoderFn.forward's arguments are numbered (x 6, E 7, the positional table
     8, then the encoder parameters in arena order from 9: cls_token, the patch projection's weight and bias, 12 per block, the final norm's two).
       asked    per encoder parameter (arena order): did it ask for a gradient — what the backward node returns one for;
@@ -531,9 +560,11 @@ def _grad_plan(need, depth: int, dp):
     assert len(asked) == 3 + 12 * depth + 2
     params = asked if dp is None else (True,) * len(asked)
     blocks = [{name: (params[3 + 12 * bi + o], params[3 + 12 * bi + o + 1]) for name, o in _LINEARS} for bi in range(depth)]
-    frozen_k = _frozen_prefix(any(need[6:12]), [any(need[12 + 12 * bi:24 + 12 * bi]) for bi in range(depth)], any(need[12 + 12 * depth:]), dp)
+    # upstream: something upstream of the blocks that is not among _EncoderFn's inputs needs a gradient (the mask token of _EncoderMaskFn)
+    frozen_k = _frozen_prefix(upstream or any(need[6:12]), [any(need[12 + 12 * bi:24 + 12 * bi]) for bi in range(depth)],
+                              any(need[12 + 12 * depth:]), dp)
     return types.SimpleNamespace(asked=asked, params=params, patch=(params[1], params[2]), blocks=blocks, frozen_k=frozen_k,
-                                 data_only=need[6] and not any(need[7:]) and dp is None)
+                                 data_only=need[6] and not any(need[7:]) and dp is None and not upstream)
 
 
 def _check_taps_above_prefix(tap_blocks, fk) -> None:
@@ -1106,7 +1137,7 @@ class DiChaViT(nn.Module):
             out.append(tuple(pair))
         return out
 
-    def _tokenise(self, x, ch_idx_dev, C, E, pos_tab, want_ortho, keep, st_scale, st_shift, tok, ops):
+    def _tokenise(self, x, ch_idx_dev, C, E, pos_tab, want_ortho, keep, st_scale, st_shift, tok, ops, mask=None):
         """The tokeniser: im2col -> MFMA GEMM with (+bias +channel_embed[c] +pos[i]) epilogue, CLS fill, ortho statistics, token gather.
         ops: the set of bf16 operand copies this forward multiplies by (_OperandCopies).  Returns (f, the residual stream [M, D], the ortho
         statistics [B, 2], what the tokeniser's backward needs); f is what the blocks of this forward share: the shapes the encoder sees, `ops`,
@@ -1127,6 +1158,10 @@ class DiChaViT(nn.Module):
         Ec, pc = E.contiguous(), pos_tab.contiguous()
         hip.gemm_nt(Xp, ops.w(pe.proj.weight), hip.EPI_PATCH, xs, bias=pe.proj.bias, out2=Y, aux=Ec, aux2=pc, T=T, n=ntok,
                     ldo=D, ldo2=D, ldaux=D)
+        if mask is not None:
+            # masked patch tokens (iBOT): the masked rows become mask_token + (E[c] + pos[1 + i]), the epilogue's bits for a projection output of
+            # mask_token.  Y keeps the real patches: the ortho regulariser acts on what the projection computed
+            hip.mask_tokens_fwd(xs, mask[0], mask[1], Ec, pc, B, Ctok, ntok, D)
         hip.fill_cls(xs, fe.cls_token, pc, B, N * D, D)
         stats = torch.zeros(B, 2, dtype=f32, device=dev)
         kept = dict(Xp=Xp)
@@ -1273,7 +1308,7 @@ class DiChaViT(nn.Module):
             hip.ln_bwd(dtap.view(B * N, D), x, stats[0], stats[1], fe.norm.weight, dx, dx, None, gw, gb, B * N, D)
 
     def _run_forward(self, x, ch_idx_dev, C, E, pos_tab, want_ortho, save, keep=None, st_scale=None, st_shift=None, tok=None, frozen_k=None,
-                     ops=None, taps=None, gplan=None):
+                     ops=None, taps=None, gplan=None, mask=None):
         """The training / eval forward: operand copies, tokeniser, blocks, final norm.  Returns the state: feat, stats and, with save, what the
         backward reads.  frozen_k=k (with save): blocks < k and the tokeniser keep nothing for the backward (they run as with save=False, on
         the same kernels); st["layers"] still has one entry per block — the backward indexes it by block number — which for blocks < k holds
@@ -1289,7 +1324,10 @@ class DiChaViT(nn.Module):
         if ops is None and not self._copies_held:
             self._refresh_own_copies(save)
         ops = self._ops if ops is None else ops
-        f, xcur, stats, kept = self._tokenise(x, ch_idx_dev, C, E, pos_tab, want_ortho, keep, st_scale, st_shift, tok, ops)
+        f, xcur, stats, kept = self._tokenise(x, ch_idx_dev, C, E, pos_tab, want_ortho, keep, st_scale, st_shift, tok, ops,
+                                              **({} if mask is None else dict(mask=mask)))
+        if mask is not None:
+            kept["mask"] = mask  # (masks, mask_token, does it need a gradient): the tokeniser's backward rewrites the masked rows of dYb
         fk = frozen_k if save else None
         gplan = gplan if save else None
         st = dict(B=f.B, C=C, n=f.n, N=f.N, M=f.M, save=save, tok=f.tok, frozen_k=fk, gplan=gplan)
@@ -1519,6 +1557,14 @@ class DiChaViT(nn.Module):
         dE = torch.zeros(Ctok, D, dtype=f32, device=dev)
         dpos = torch.zeros(ntok + 1, D, dtype=f32, device=dev)
         hip.patch_bwd(dx, dYl, dYb, dE, dpos, g(fe.cls_token), B, Ctok, ntok, D)
+        if st.get("mask") is not None:
+            # masked patch tokens: their dx goes to the mask token (and stays in dE and dpos, which patch_bwd has added); their dYb rows keep the
+            # ortho gradient only, so the projection's weight, its bias and the input images see no token gradient from a masked patch
+            masks, _, need_mt = st["mask"]
+            dmt = torch.zeros(D, dtype=f32, device=dev)
+            hip.mask_tokens_bwd(dx, masks, dYl, dYb, dmt, B, Ctok, ntok, D)
+            if need_mt and st.get("mask_out") is not None:
+                st["mask_out"]["dmask_token"] = dmt.view(1, 1, D)
         if st.get("dx_req"):
             # input images: dYb (the token gradients with the ortho term) through the projection's adjoint; the real (C, n), also when the
             # positional table is per token (tok = (1, C*n)): dYb's rows are (b, c, i, j) either way
@@ -1614,16 +1660,21 @@ class DiChaViT(nn.Module):
         of the final norm's own backward.  A tap without a gradient launches nothing in the backward; a loss on the taps alone works.  With
         freeze_prefix(k) a tap at block l >= k - 1 works (at l = k - 1 its gradient reaches only `norm`); one below raises ValueError — no
         trainable block could receive it, and get_intermediate_layers returns that feature.
+        masks= (keyword, as in forward): a uint8 or bool GPU tensor [B, C n] for this forward's C and n; the masked patch tokens enter block 0 as
+        feature_extractor.mask_token (add_mask_token()) plus their channel and positional embeddings, and the mask token receives the gradient
+        of those rows — a mask token that requires a gradient counts as upstream of the blocks, so no frozen prefix applies.  The ortho
+        regulariser keeps acting on the real patches.  ValueError: no mask token, a mask of another shape, HCS sampling that draws a subset
+        or dropout_tokens_hcs active in this forward; NotImplementedError with a DataParallel reducer.
         Not supported: GraphedTrainStep, create_graph=True, several pools in one call."""
         depth = len(self.feature_extractor.blocks)
         blocks = _parse_layers(layers, depth)
         if pool not in (None, "channel", "cls"):
             raise ValueError(f"pool={pool!r}: expected 'channel', 'cls' or None")
-        _check_taps_above_prefix(blocks, self._host_frozen_prefix(x))
+        _check_taps_above_prefix(blocks, self._host_frozen_prefix(x, kwargs.get("masks") is not None))
         with torch.autocast(device_type="cuda", enabled=False):
             return self._forward_impl(x, chunk_name, training_chunks, init_first_layer, new_channel_init, taps=(blocks, pool), **kwargs)
 
-    def forward_views(self, views, chunk_name: str, training_chunks: Optional[str] = None, *, pool="cls", **kwargs):
+    def forward_views(self, views, chunk_name: str, training_chunks: Optional[str] = None, *, pool="cls", masks=None, patch_views=(), **kwargs):
         """Several forwards under ONE set of bf16 operand copies (multi-crop self-distillation: ssl.DINOLoss).  views: a sequence of image batches,
         e.g. [x_global (2B, 224 x 224), x_local (8B, 96 x 96)]; each runs as forward_with_features(x, chunk_name, training_chunks, layers=1,
         pool="cls", ...) runs it — its own _EncoderFn node and saved state, its own HCS and DropPath draws, the positional table resampled to its
@@ -1636,6 +1687,12 @@ class DiChaViT(nn.Module):
         every node hands autograd a private copy of its parameter gradients (they meet in one backward, where the shared gradient arena cannot
         be told free from in use); .grad is their sum and does not live in the arena, so HipAdamW takes its per-parameter path for that step.  The classifier head's output is not returned (its parameters receive no
         gradient from this call: freeze them or leave them out of the optimiser).
+        Masked patch-token distillation (ssl.IBOTPatchLoss): masks — a list with one entry per view, a mask (uint8 or bool [B_v, C n_v], see
+        forward_with_features) or None; patch_views — the indices of the views whose final-normed patch tokens are returned too.  With patch_views
+        non-empty the call returns (feats, extra, patches): patches[v] is fp32 [B_v, C n_v, D] for the listed views (the CLS row dropped, connected
+        to the graph) and None for the others.  A listed view runs its tap with pool=None, so its last block runs on all rows; the others keep
+        the CLS-only tail.  CLS and patch gradients of a view arrive through its one node.  With masks=None and patch_views=() the call launches
+        exactly what it launched before these arguments existed and returns the same 2-tuple.
         Not supported: a DataParallel reducer (NotImplementedError: its begin_forward() assumes one forward per backward), GraphedTrainStep, a
         pool other than "cls"."""
         if pool != "cls":
@@ -1643,6 +1700,12 @@ class DiChaViT(nn.Module):
         views = list(views)
         if not views:
             raise ValueError("forward_views: no views")
+        masks = [None] * len(views) if masks is None else list(masks)
+        patch_views = sorted({int(v) for v in patch_views})
+        if len(masks) != len(views):
+            raise ValueError("forward_views: masks has one entry per view (a mask or None)")
+        if any(not 0 <= v < len(views) for v in patch_views):
+            raise ValueError(f"forward_views: patch_views names views 0 .. {len(views) - 1}")
         for x in views:
             self._check_input(x)
         if self._dp is not None:
@@ -1656,29 +1719,38 @@ class DiChaViT(nn.Module):
         # will the nodes save for a backward (_EncoderFn: any(needs_input_grad)), from requires_grad flags alone, as _host_grad_plan reads them
         save = torch.is_grad_enabled() and (any(x.requires_grad for x in views) or fe.pos_embed.requires_grad or
                                             (hasattr(pe, "channel_embed") and pe.channel_embed.weight.requires_grad) or
-                                            any(p.requires_grad for p in self._enc_param_list()))
+                                            any(p.requires_grad for p in self._enc_param_list()) or
+                                            (any(m is not None for m in masks) and getattr(fe, "mask_token", None) is not None
+                                             and fe.mask_token.requires_grad))
         with torch.autocast(device_type="cuda", enabled=False):
             self._refresh_own_copies(save)
         self._copies_held = len(views)
         try:
-            feats, extra = [], None
-            for x in views:
-                out, taps = self.forward_with_features(x, chunk_name, training_chunks, layers=1, pool="cls", **kwargs)
-                feats.append(taps[0])
+            feats, extra, patches = [], None, [None] * len(views)
+            for v, x in enumerate(views):
+                kw = kwargs if masks[v] is None else dict(kwargs, masks=masks[v])
+                if v in patch_views:  # every normed token of the last block: row 0 the CLS feature, the rest the patch tokens
+                    out, taps = self.forward_with_features(x, chunk_name, training_chunks, layers=1, pool=None, **kw)
+                    feats.append(taps[0][:, 0])
+                    patches[v] = taps[0][:, 1:]
+                else:
+                    out, taps = self.forward_with_features(x, chunk_name, training_chunks, layers=1, pool="cls", **kw)
+                    feats.append(taps[0])
                 if self.training:
                     extra = out[1] if extra is None else extra + out[1]
         finally:
             self._copies_held = 0
         feats = torch.cat(feats, dim=0)
-        return feats, (extra if extra is not None else feats.new_zeros(()))
+        extra = extra if extra is not None else feats.new_zeros(())
+        return (feats, extra, patches) if patch_views else (feats, extra)
 
-    def _host_frozen_prefix(self, x) -> Optional[int]:
+    def _host_frozen_prefix(self, x, masked: bool = False) -> Optional[int]:
         """_frozen_prefix as _EncoderFn will find it for a forward of x, from requires_grad flags alone (no device work): upstream of the blocks are
-        x and what the node's E, pos_tab, cls_token and patch-projection inputs come from."""
-        plan = self._host_grad_plan(x)
+        x and what the node's E, pos_tab, cls_token and patch-projection inputs come from — and, in a forward with masks, the mask token."""
+        plan = self._host_grad_plan(x, masked)
         return None if plan is None else plan.frozen_k
 
-    def _host_grad_plan(self, x=None):
+    def _host_grad_plan(self, x=None, masked: bool = False):
         """_grad_plan as _EncoderFn will find it for a forward of x, from requires_grad flags alone (no device work); None when no graph is
         recorded.  The node's E input comes from channel_embed, its positional table from pos_embed."""
         if not torch.is_grad_enabled():
@@ -1687,23 +1759,39 @@ class DiChaViT(nn.Module):
         pe = fe.patch_embed
         need = [False] * 6 + [torch.is_tensor(x) and x.requires_grad, hasattr(pe, "channel_embed") and pe.channel_embed.weight.requires_grad,
                               fe.pos_embed.requires_grad] + [p.requires_grad for p in self._enc_param_list()]
-        return _grad_plan(need, len(fe.blocks), self._dp)
+        mt = getattr(fe, "mask_token", None)
+        return _grad_plan(need, len(fe.blocks), self._dp, upstream=bool(masked and mt is not None and mt.requires_grad))
 
     def _forward_impl(self, x: torch.Tensor, chunk_name: str, training_chunks: Optional[str] = None, init_first_layer=None,
-                      new_channel_init=None, taps=None, **kwargs):
+                      new_channel_init=None, taps=None, masks=None, **kwargs):
         self._check_input(x)
+        if masks is not None:
+            if getattr(self.feature_extractor, "mask_token", None) is None:
+                raise ValueError("masks= needs a mask token: call model.add_mask_token() first (before the optimiser and the teacher are built)")
+            if self._dp is not None:
+                raise NotImplementedError("masks= with a DataParallel reducer attached: the reducer's buckets do not cover the mask token")
+            if self.training and self.feature_extractor.patch_embed.enable_sample:
+                # before the draw: a subset — or the full set in another order — would give the student other tokens than the teacher's
+                raise ValueError("masks= while HCS channel sampling draws a subset in this forward: teacher and student must see the same "
+                                 "tokens (switch enable_sample off, or run in eval mode)")
         if self._dp is not None and self.training:
             self._dp.begin_forward()
         tk = self._prepare_tokens(x, chunk_name, training_chunks, new_channel_init)
+        if masks is not None:
+            masks = self._check_masks(masks, x, tk)
         self._cur_scale, self._cur_shift = tk.scale, tk.shift  # the affine rows of the channels used by this forward
         x, C, n, want_ortho, cur_channels, channel_embed = tk.x, tk.C, tk.n, tk.want_ortho, tk.cur_channels, tk.channel_embed
         lam_o, lam_p = tk.lam_o, tk.lam_p
         pe = self.feature_extractor.patch_embed
         feats = None
-        if taps is not None:
-            if taps[1] == "channel" and tk.keep is not None:
-                raise ValueError("pool='channel' needs every channel's n_p patch tokens: with dropout_tokens_hcs active in train mode the channel "
-                                 "segments are ragged (pool=None returns the kept tokens)")
+        if taps is not None and taps[1] == "channel" and tk.keep is not None:
+            raise ValueError("pool='channel' needs every channel's n_p patch tokens: with dropout_tokens_hcs active in train mode the channel "
+                             "segments are ragged (pool=None returns the kept tokens)")
+        if masks is not None:
+            feat, stats, *feats = _EncoderMaskFn.apply(masks, self.feature_extractor.mask_token, taps, self, tk.ch_idx_dev, C, want_ortho, tk.keep,
+                                                       tk.tok, x, tk.E_tok, tk.pos_tab, *self._enc_params)
+            feats = feats if taps is not None else None
+        elif taps is not None:
             feat, stats, *feats = _EncoderTapsFn.apply(taps, self, tk.ch_idx_dev, C, want_ortho, tk.keep, tk.tok, x, tk.E_tok, tk.pos_tab, *self._enc_params)
         else:
             feat, stats = _EncoderFn.apply(self, tk.ch_idx_dev, C, want_ortho, tk.keep, tk.tok, x, tk.E_tok, tk.pos_tab, *self._enc_params)
@@ -1724,6 +1812,27 @@ class DiChaViT(nn.Module):
                 extra = out.new_zeros(())  # :857-858 (a device-side fill: torch.tensor(0.0, device=...) is a synchronising host-to-device copy)
             out = (out, extra)
         return out if feats is None else (out, feats)
+
+    def add_mask_token(self) -> nn.Parameter:
+        """Masked patch-token distillation (ssl.IBOTPatchLoss): creates feature_extractor.mask_token, an nn.Parameter of zeros [1, 1, D], which
+        forward(..., masks=) writes in place of the masked patches' projection output.  Call it BEFORE the optimiser and the teacher
+        (AveragedModel) are built: the parameter arena is rebuilt on the next forward with the mask token among the non-encoder parameters, so
+        HipAdamW, AveragedModel and checkpoints see it like any other of them.  Without this call the state dict is exactly what it was."""
+        fe = self.feature_extractor
+        if getattr(fe, "mask_token", None) is None:
+            fe.mask_token = nn.Parameter(torch.zeros(1, 1, self.dim, dtype=torch.float32, device=fe.cls_token.device))
+            self._arena = None  # _ensure_arena rebuilds
+        return fe.mask_token
+
+    def _check_masks(self, masks, x, tk):
+        """masks= of a forward against the tokens it prepared: uint8 or bool [B, C n] on x's device -> uint8, contiguous."""
+        if tk.keep is not None:
+            raise ValueError("masks= with dropout_tokens_hcs active in train mode: the dropped tokens and the masked ones would overlap")
+        if not torch.is_tensor(masks) or masks.dtype not in (torch.uint8, torch.bool) or masks.device != x.device or \
+                tuple(masks.shape) != (x.shape[0], tk.C * tk.n):
+            raise ValueError(f"masks: expected a uint8 or bool tensor [{x.shape[0]}, {tk.C * tk.n}] (B, C * n of this forward) on {x.device}")
+        masks = masks.contiguous()
+        return masks.view(torch.uint8) if masks.dtype == torch.bool else masks
 
     @staticmethod
     def _check_input(x: torch.Tensor) -> None:

@@ -86,6 +86,13 @@ _SIGS = {
     "dcv_dino_loss_fwd": ([_vp, _l, _vp, _l, _vp, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _l, _vp], _i),
     "dcv_dino_loss_bwd": ([_vp, _l, _vp, _l, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _vp, _l, _vp], _i),
     "dcv_dino_loss_plan": ([_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i),
+    "dcv_ibot_loss_ws_floats": ([_i, _i], _l),
+    "dcv_ibot_loss_fwd": ([_vp, _l, _vp, _l, _vp, _vp, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _l, _vp], _i),
+    "dcv_ibot_loss_bwd": ([_vp, _l, _vp, _l, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _f, _vp, _l, _vp], _i),
+    "dcv_ibot_loss_plan": ([_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _i),
+    "dcv_mask_tokens_fwd": ([_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp], _i),
+    "dcv_mask_tokens_bwd_ws_floats": ([_i, _i, _i, _i], _l),
+    "dcv_mask_tokens_bwd": ([_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _l, _vp], _i),
     "dcv_adamw": ([_vp, _vp, _vp, _vp, _l, _f, _f, _f, _f, _f, _i, _f, _vp], _i),
     "dcv_adamw_dyn": ([_vp, _vp, _vp, _vp, _l, _vp, _vp], _i),
     "dcv_adamw_set_hyper": ([_vp, _f, _f, _f, _f, _f, _i, _f, _vp], _i),
@@ -446,6 +453,76 @@ def dino_loss_bwd(S, T, center, V, student_temp, teacher_temp, s_stats, t_stats,
     _check(rc, "dcv_dino_loss_bwd")
 
 
+def ibot_loss_ws_floats(R, K) -> int:
+    return _ws_size(load().dcv_ibot_loss_ws_floats(R, K))
+
+
+def ibot_loss_plan(R, K, aligned=True) -> dict:
+    """The launch plan of ibot_loss_fwd / ibot_loss_bwd (include/dcv.h: dcv_ibot_loss_plan) — host logic, callable without a GPU."""
+    vec, tile_cols, col_tiles, chunk_rows, chunks, wpw, grid, passes = (C.c_int() for _ in range(8))
+    items = C.c_long()
+    rc = load().dcv_ibot_loss_plan(R, K, int(bool(aligned)), C.addressof(vec), C.addressof(tile_cols), C.addressof(col_tiles),
+                                   C.addressof(chunk_rows), C.addressof(chunks), C.addressof(items), C.addressof(wpw), C.addressof(grid),
+                                   C.addressof(passes))
+    _check(rc, "dcv_ibot_loss_plan")
+    return dict(vec=vec.value, tile_cols=tile_cols.value, col_tiles=col_tiles.value, chunk_rows=chunk_rows.value, chunks=chunks.value,
+                items=items.value, waves_per_wg=wpw.value, grid=grid.value, passes=passes.value)
+
+
+def _ibot_operands(S, T, center, weights):
+    for t, name in ((S, "S"), (T, "T")):
+        if not t.is_cuda:
+            raise RuntimeError(f"{name}: expected a GPU tensor (the HIP path has no CPU fallback)")
+        if t.dtype != torch.float32:
+            raise RuntimeError(f"{name}: expected {torch.float32}, got {t.dtype}")
+        if t.dim() != 2 or t.stride(1) != 1:
+            raise RuntimeError(f"{name}: expected a [rows, K] tensor with unit column stride")
+    _req(center, torch.float32, "center"); _req(weights, torch.float32, "weights")
+    R, K = S.shape
+    if R < 1 or T.shape != S.shape or center.numel() != K or weights.numel() != R:
+        raise ValueError("ibot_loss: S and T hold R >= 1 rows of K logits, center K floats, weights R")
+    return R, K
+
+
+def ibot_loss_fwd(S, T, center, weights, student_temp, teacher_temp, loss, s_stats=None, t_stats=None, tsum=None, ws=None):
+    """loss[0] = the masked patch-token distillation loss of the student logits S [R, K] against the teacher logits T [R, K] (row r of both the
+    same token), the centre and the row weights (include/dcv.h: dcv_ibot_loss_fwd); rows S.stride(0) / T.stride(0) >= K apart.  s_stats [R, 3],
+    t_stats [R, 4]: the row statistics ibot_loss_bwd reads; tsum [K]: the unweighted column sums of T; each written unless None.  Always
+    deterministic: the kernels have no other form.  ws: the caller's workspace of >= ibot_loss_ws_floats(R, K) floats (tests); by default the
+    stream's shared one."""
+    R, K = _ibot_operands(S, T, center, weights)
+    _req(loss, torch.float32, "loss")
+    for t, name, n in ((s_stats, "s_stats", 3 * R), (t_stats, "t_stats", 4 * R), (tsum, "tsum", K)):
+        if t is not None:
+            _req(t, torch.float32, name)
+            if t.numel() < n:
+                raise ValueError(f"ibot_loss_fwd: {name} holds {n} floats")
+    lib = load()
+    if ws is None:
+        ws = _workspace(_ws_size(lib.dcv_ibot_loss_ws_floats(R, K)), S)
+    else:
+        _req(ws, torch.float32, "ws")
+    with _timer(lambda: ("ibot_loss_fwd_kernel", f"R{R} K{K}", 0.0, None, 4.0 * K * (2 * R + 1))):
+        rc = lib.dcv_ibot_loss_fwd(_p(S), S.stride(0), _p(T), T.stride(0), _p(center), _p(weights), R, K, float(student_temp), float(teacher_temp),
+                                   _p(loss), _p(s_stats), _p(t_stats), _p(tsum), _p(ws), ws.numel(), _stream())
+    _check(rc, "dcv_ibot_loss_fwd")
+
+
+def ibot_loss_bwd(S, T, center, weights, student_temp, teacher_temp, s_stats, t_stats, g, dS):
+    """dS [R, K] (rows dS.stride(0) >= K apart) = g[0] * d loss / d S from the statistics ibot_loss_fwd saved (include/dcv.h: dcv_ibot_loss_bwd);
+    g: the incoming gradient, one float on the device."""
+    R, K = _ibot_operands(S, T, center, weights)
+    _req(s_stats, torch.float32, "s_stats"); _req(t_stats, torch.float32, "t_stats"); _req(g, torch.float32, "g")
+    if not dS.is_cuda or dS.dtype != torch.float32 or dS.dim() != 2 or dS.stride(1) != 1 or dS.shape != S.shape:
+        raise RuntimeError("dS: expected a float32 GPU tensor of S's shape with unit column stride")
+    if s_stats.numel() < 3 * R or t_stats.numel() < 4 * R or g.numel() != 1:
+        raise ValueError("ibot_loss_bwd: s_stats holds 3*R floats, t_stats 4*R, g one")
+    with _timer(lambda: ("ibot_loss_bwd_kernel", f"R{R} K{K}", 0.0, None, 4.0 * K * (3 * R + 1))):
+        rc = load().dcv_ibot_loss_bwd(_p(S), S.stride(0), _p(T), T.stride(0), _p(center), _p(weights), _p(s_stats), _p(t_stats), _p(g), R, K,
+                                      float(student_temp), float(teacher_temp), _p(dS), dS.stride(0), _stream())
+    _check(rc, "dcv_ibot_loss_bwd")
+
+
 def ln_fwd(x, gamma, beta, out, mean, rstd, M, D, eps, x_row_stride=None):
     with _timer(lambda: (f"ln_fwd_kernel<{'true' if out.dtype == torch.float32 else 'false'}, {2 if D <= 512 else 4}>", f"M{M} D{D}", 0.0, None,
                          M * D * (4.0 + (4.0 if out.dtype == torch.float32 else 2.0)))):
@@ -665,6 +742,45 @@ def patch_bwd(dx0, dYloss, dY_bf16, dE, dpos, dcls, B, C, n, D):
     else:
         rc = lib.dcv_patch_bwd(_p(dx0), _p(dYloss), _p(dY_bf16), _p(dE), _p(dpos), _p(dcls), B, C, n, D, _stream())
     _check(rc, "dcv_patch_bwd")
+
+
+def _mask_arg(mask, B, C, n):
+    if not mask.is_cuda or mask.dtype not in (torch.uint8, torch.bool) or not mask.is_contiguous() or mask.numel() != B * C * n:
+        raise RuntimeError("mask: expected a contiguous uint8 or bool GPU tensor [B, C * n]")
+    return mask
+
+
+def mask_tokens_fwd(xs, mask, mask_token, E, pos, B, C, n, D):
+    """xs [B, 1 + C n, D]: the masked token rows (mask uint8 [B, C n] != 0) become mask_token + (E[c] + pos[1 + i]), the EPI_PATCH epilogue's
+    bits for a projection output of mask_token (include/dcv.h: dcv_mask_tokens_fwd).  Nothing else is written."""
+    for t, name in ((xs, "xs"), (mask_token, "mask_token"), (E, "E"), (pos, "pos")):
+        _req(t, torch.float32, name)
+    if xs.numel() != B * (1 + C * n) * D or mask_token.numel() != D or E.numel() < C * D or pos.numel() < (1 + n) * D:
+        raise ValueError("mask_tokens_fwd: xs holds B (1 + C n) D floats, mask_token D, E C D, pos (1 + n) D")
+    _mask_arg(mask, B, C, n)
+    with _timer(lambda: ("mask_tokens_fwd_kernel", f"B{B} C{C} n{n} D{D}", 0.0, None, 1.0 * B * C * n)):
+        rc = load().dcv_mask_tokens_fwd(_p(xs), _p(mask), _p(mask_token), _p(E), _p(pos), B, C, n, D, _stream())
+    _check(rc, "dcv_mask_tokens_fwd")
+
+
+def mask_tokens_bwd(dx0, mask, dYloss, dY_bf16, dmask_token, B, C, n, D, ws=None):
+    """After patch_bwd: dmask_token [D] += the masked rows' dx0[b, 1 + t, :]; the masked rows of dY_bf16 [B C n, D] become bf16(dYloss row), or 0
+    when dYloss is None (include/dcv.h: dcv_mask_tokens_bwd).  No atomics in either reduction mode: partials through the workspace."""
+    _req(dx0, torch.float32, "dx0"); _req(dY_bf16, torch.bfloat16, "dY_bf16"); _req(dmask_token, torch.float32, "dmask_token")
+    if dYloss is not None:
+        _req(dYloss, torch.float32, "dYloss")
+    if (dx0.numel() != B * (1 + C * n) * D or dY_bf16.numel() != B * C * n * D or dmask_token.numel() != D
+            or (dYloss is not None and dYloss.numel() != B * C * n * D)):
+        raise ValueError("mask_tokens_bwd: dx0 holds B (1 + C n) D floats, dY_bf16 and dYloss B C n D, dmask_token D")
+    _mask_arg(mask, B, C, n)
+    lib = load()
+    if ws is None:
+        ws = _workspace(_ws_size(lib.dcv_mask_tokens_bwd_ws_floats(B, C, n, D)), dx0)
+    else:
+        _req(ws, torch.float32, "ws")
+    with _timer(lambda: ("mask_tokens_bwd_kernel", f"B{B} C{C} n{n} D{D}", 0.0, None, 1.0 * B * C * n)):
+        rc = lib.dcv_mask_tokens_bwd(_p(dx0), _p(mask), _p(dYloss), _p(dY_bf16), _p(dmask_token), B, C, n, D, _p(ws), ws.numel(), _stream())
+    _check(rc, "dcv_mask_tokens_bwd")
 
 
 def gather_tokens(x, idx, out, B, N, Nk, D, scatter=False):

@@ -371,6 +371,52 @@ int dcv_dino_loss_bwd(const float* S, long lds, const float* T, long ldt, const 
 int dcv_dino_loss_plan(int V, int B, int K, int aligned, int* vec, int* tile_cols, int* col_tiles, long* items, int* waves_per_wg, int* grid,
                        int* passes);
 
+/* iBOT's masked patch-token distillation loss (Zhou et al. 2022; the patch term of DINOv2), value and gradient, fp32 in and out (csrc/
+ * ibot_loss.hip).  S: student logits [R, K], rows lds floats apart; T: teacher logits [R, K], rows ldt apart, row r of both the same masked token;
+ * center [K]; weights [R].  With q_r = softmax((T_r - center) / teacher_temp) and p_r = softmax(S_r / student_temp):
+ *   loss[0] = sum_r weights[r] (lse(S_r / student_temp) - <q_r, S_r> / student_temp)                        (dcv_ibot_loss_fwd)
+ *   dS[r,k] = g[0] weights[r] (p_r[k] - q_r[k]) / student_temp, rows ldd apart, written once              (dcv_ibot_loss_bwd)
+ *   tsum[k] = sum_r T[r,k], unweighted: the centre's statistics                                           (dcv_ibot_loss_fwd, unless NULL)
+ * g is read on the device.  The forward is three launches: one pass over S, T and center that leaves per-(row, column tile) partial maxima,
+ * sums of exponentials and dots and, per chunk of 32 rows, the chunk's column sums of T (in double) in ws; a finish that merges a row's records in
+ * tile order and, beside that, adds the chunks' column sums in a fixed order (tsum's second level: T is read once); and a one-block sum of the R
+ * weighted row terms (in double).  s_stats [R, 3]: per row (max, sum of exponentials relative to it as a high and a low float: the sums are formed in double) of S /
+ * student_temp; t_stats [R, 4]: per row (max, the max's low part, sum high, sum low) of (T - center) / teacher_temp with T - center carried as fl(T - center) plus its exact rounding error; each
+ * written unless NULL, and what the backward reads.  The backward is one launch: S, T, center read once more, dS written once; no probability
+ * tensor ever reaches memory.  ALWAYS deterministic: no atomics, and every summation order is a function of (R, K) alone — not of the data, the
+ * weights, the strides, the alignment or the grid.  A row of weight 0 adds exactly 0 to the loss and its dS row is exactly 0.  16-byte loads and
+ * stores when every matrix pointer is 16-byte aligned and K and every stride are multiples of 4, 4-byte ones on the same columns otherwise;
+ * columns >= K of a row are never read (padding may hold anything).  ws: at least dcv_ibot_loss_ws_floats(R, K) floats, contents irrelevant before
+ * and after.  Checked before any HIP call: a required pointer NULL -> DCV_ERR_NULL; R < 1, K < 1, a stride below K, a temperature that is not
+ * positive, ws_floats too small -> DCV_ERR_SHAPE; a row of 2 GB or more (with its last tile) -> DCV_ERR_UNSUPPORTED; a pointer off 4 bytes
+ * (ws: 16) -> DCV_ERR_ALIGN. */
+long dcv_ibot_loss_ws_floats(int R, int K);
+int dcv_ibot_loss_fwd(const float* S, long lds, const float* T, long ldt, const float* center, const float* weights, int R, int K,
+                      float student_temp, float teacher_temp, float* loss, float* s_stats, float* t_stats, float* tsum, float* ws, long ws_floats,
+                      void* stream);
+int dcv_ibot_loss_bwd(const float* S, long lds, const float* T, long ldt, const float* center, const float* weights, const float* s_stats,
+                      const float* t_stats, const float* g, int R, int K, float student_temp, float teacher_temp, float* dS, long ldd, void* stream);
+/* their launch plan — host logic, no GPU call.  A row's columns fall into col_tiles tiles of tile_cols = 1024 and the rows into chunks =
+ * ceil(R / chunk_rows) chunks of chunk_rows = 32 consecutive rows; one wave owns one item = (chunk, tile), item = chunk * col_tiles + tile, and
+ * walks the chunk's rows in row order; lane l holds the 16 columns tile * tile_cols + (64 u + l) * 4 + e, u, e < 4, loaded vec = 4 or 1 floats at
+ * a time.  A workgroup is waves_per_wg = 4 waves; wave w of workgroup x takes in pass r the item (x + r * grid) * waves_per_wg + w (none past
+ * `items`); grid = min(ceil(items / 4), 2048), passes = 1 below the cap.  ws holds 2 (6 R col_tiles + R + chunks K) floats (doubles: the records, the row terms, tsum's first level). */
+int dcv_ibot_loss_plan(int R, int K, int aligned, int* vec, int* tile_cols, int* col_tiles, int* chunk_rows, int* chunks, long* items,
+                       int* waves_per_wg, int* grid, int* passes);
+
+/* The learned mask token of masked-patch distillation at the tokeniser's seam (csrc/mask_tokens.hip).  mask: uint8 [B, C n], nonzero = masked.
+ * dcv_mask_tokens_fwd, after the DCV_EPI_PATCH GEMM: every masked token row (b, t = c n + i) gets xs[b, 1 + t, :] = mask_token + (E[c] +
+ * pos[1 + i]) — the bits the epilogue writes for a row whose acc + bias equals mask_token; nothing else is written (xs f32 [B, 1 + C n, D], E
+ * [C, D], pos [1 + n, D], mask_token [D], 16-byte aligned).
+ * dcv_mask_tokens_bwd, after dcv_patch_bwd: dmask_token[D] += the sum of dx0[b, 1 + t, :] over the masked rows, and the masked rows of dY_bf16
+ * [B C n, D] become bf16(dYloss row), or 0 when dYloss is NULL.  No atomics: parts of 256 consecutive rows of the flat (b, t) range, 256 / (D / 4)
+ * sub-lanes per part, partials through ws (>= dcv_mask_tokens_bwd_ws_floats floats), added in index order.  D % 4 == 0, D <= 1024. */
+int dcv_mask_tokens_fwd(float* xs, const unsigned char* mask, const float* mask_token, const float* E, const float* pos, int B, int C, int n, int D,
+                        void* stream);
+long dcv_mask_tokens_bwd_ws_floats(int B, int C, int n, int D);
+int dcv_mask_tokens_bwd(const float* dx0, const unsigned char* mask, const float* dYloss, void* dY_bf16, float* dmask_token, int B, int C, int n,
+                        int D, float* ws, long ws_floats, void* stream);
+
 /* fused AdamW over a flat fp32 range; g is multiplied by grad_scale first (1/world for data parallel). */
 int dcv_adamw(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2, float eps,
               float weight_decay, int step, float grad_scale, void* stream);
